@@ -2,6 +2,7 @@
 """Benchmark: train images/sec of the VanillaVAE training step on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--arch vanilla|betaH|iwae|vq]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 With --gpus N > 1 and no RANK in the environment, this process starts the N rank processes
@@ -17,6 +18,18 @@ per GPU (weak scaling, data parallel over ranks, RCCL gradient all-reduce), bf16
 accumulation / statistics / optimizer.  A "step" = forward + ELBO + backward + [all-reduce] + Adam
 (experiment.py:45-86 + :308-311), inputs already resident in HBM, the whole step replayed from
 HIP graphs.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, runs W untimed and K timed steps and prints the line.  With --dump-outputs
+DIR it then puts the seeded start state back (parameters, BatchNorm statistics, Adam moments, step
+counter), replays the timed step once more and writes what that step computed as DIR/<name>.npy
+(dump_outputs): inputs and state are the same in every run, so two builds run with the same
+arguments can be compared output for output.  The dumped step starts from the start state because
+the state after K + W steps cannot be compared: the bf16 step sums its BatchNorm statistics with
+float atomics, and this workload's optimizer steps amplify that rounding to differences of order
+one within a few steps (an fp32 run reproduces bit for bit).  The updated parameters are left out
+for the same reason: Adam's first update is lr * sign(g), which turns the rounding of a
+near-zero gradient into a full step.  --full adds the legs below, all measured after the timed
+region: roofline / step_roofline, dropin / dropin_eager (dropin_leg) and the CPU baselines.
 
 roofline: the dominant kernel of the step (largest time per step, measured with HIP events on the
 stream it runs on, each launch isolated behind a spin kernel so the events bracket only it) with
@@ -94,7 +107,18 @@ def parse():
     ap.add_argument("--kernel-breakdown", action="store_true", help="print per-kernel times to stderr")
     ap.add_argument("--selftest", action="store_true",
                     help="CPU stand-in step (launcher / timing / output contract check; no GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: per-call kernel "
+                         "times and the rooflines, the drop-in path legs, the CPU baselines (--no-dropin, "
+                         "--no-cpu-baseline, --cpu-seconds and --kernel-breakdown act here)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps replay the timed step once from the seeded start state and write "
+                         "what it computed (loss terms, reconstruction, gradients, BatchNorm statistics) as "
+                         "DIR/<name>.npy, rank 0's")
+    args = ap.parse_args()
+    if args.kernel_breakdown and not args.full:
+        ap.error("--kernel-breakdown prints what --full measures: pass --full")
+    return args
 
 
 # ----------------------------------------------------------------------------- rank launcher
@@ -580,6 +604,107 @@ def dropin_leg(args, dtype, steps=None, warmup=3, engine="graph"):
             "steps": steps, "path": path, "loss": float(exp.logged["loss"])}
 
 
+DUMP_BUDGET = 60_000_000        # bytes of --dump-outputs files in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """Write what the dumped step left its caller as path/<name>.npy (float32, loss_terms float64):
+    the loss terms, the reconstruction, the gradients and the updated BatchNorm running statistics.
+    The budget is shared smallest array first; an array over its
+    share is written as a sample at fixed indices (drawn with seed 1265 from its size alone, sorted),
+    the same in every run and build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    todo = sorted(arrays.items(), key=lambda kv: kv[1].numel() * kv[1].element_size())
+    for i, (name, t) in enumerate(todo):
+        t = t.detach().reshape(-1)
+        share = left // (len(todo) - i) // t.element_size()
+        if t.numel() > share:
+            idx = torch.randint(t.numel(), (share,), generator=torch.Generator().manual_seed(1265)).sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def full_report(args, plan, dtype, dsz, world, ms):
+    """What --full adds to the result line, measured after the timed region (and after its outputs
+    were read): the per-call kernel times and rooflines, the drop-in path legs and the CPU baselines."""
+    # ---- dominant kernel: per-launch time with HIP events on the step's stream
+    times = time_kernels(plan)
+    costs = kernel_costs(plan, dsz)
+    rows, rows_ref = [], []
+    for (fn, ref, us), (_, _, fl, by) in zip(times, costs):
+        rows.append((us, fn, fl, by))
+        rows_ref.append(ref)
+    if args.kernel_breakdown:
+        for us, fn, fl, by in rows:
+            print(f"{fn:28s} {us:9.2f} us  {fl / 1e9:8.3f} GF  {by / 1e6:8.2f} MB  "
+                  f"{(fl / us / 1e6) if us else 0:8.1f} TF/s  {(by / us / 1e3) if us else 0:8.1f} GB/s",
+                  file=sys.stderr)
+    idx = max(range(len(rows)), key=lambda i: rows[i][0])
+    us, fn, fl, by = rows[idx]
+    ai = fl / by if by else 0.0
+    peak_tf = MFMA_PEAK_TFLOPS[args.dtype]
+    ridge = peak_tf * 1e12 / (HBM_PEAK_GBS * 1e9)
+    if ai >= ridge:
+        roof = {"bound": "mfma", "achieved": round(fl / (us * 1e-6) / 1e12, 3), "peak": peak_tf, "unit": "TFLOP/s"}
+    else:
+        roof = {"bound": "hbm", "achieved": round(by / (us * 1e-6) / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s"}
+    roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
+    from vae_amd import _lib as L
+    digest = L.load().vae_build_digest().decode()
+    kernels = call_kernels(fn, rows_ref[idx])
+    tr, why_tr = pmc_traffic(kernels, digest, args.arch, args.batch)
+    roof["traffic"] = tr["bytes"] if tr else None
+    roof["traffic_ratio"] = round(tr["bytes"] / by, 3) if tr and by else None
+    roof["traffic_source"] = tr if tr else {"missing": why_tr}
+    roof["kernel"] = f"{fn} (call #{idx} of the step; its kernels: {', '.join(k[1] for k in kernels) or 'n/a'})"
+    roof["us_per_launch"] = round(us, 2)
+    rp, why_rp = rocprof_times(kernels, digest, args.arch, args.batch)
+    if rp and abs(rp["sum_avg_us"] - us) > PAIR_TOL * us:
+        # the profile's kernels do not account for this call's measured time: not the same work
+        # (another plan or launch count), so neither its times nor its counters are evidence here
+        why = (f"{rp['file']}: rocprof sum {rp['sum_avg_us']} us vs {us:.2f} us event time "
+               f"(> {PAIR_TOL:.0%} apart)")
+        rp, why_rp = None, why
+        roof["traffic"] = roof["traffic_ratio"] = None
+        roof["traffic_source"] = {"missing": why}
+    roof["rocprof"] = rp if rp else {"missing": why_rp}
+    roof["build_digest"] = digest
+    roof["algorithmic"] = {"flops": fl, "bytes": by, "ai_flop_per_byte": round(ai, 1)}
+    step_kernel_us = sum(r[0] for r in rows)
+    # SURVEY §8(d): the step-level attainable time — every kernel at its own roofline bound,
+    # max(flops / MFMA peak, bytes / HBM peak), summed — over the measured step time; and the
+    # literal MFMA fraction, all of the step's flops over the measured step at the bf16/fp32 peak
+    attain_us = sum(max(fl_ / (peak_tf * 1e6), by_ / (HBM_PEAK_GBS * 1e3)) for _, _, fl_, by_ in rows)
+    step_flops = sum(r[2] for r in rows)
+
+    cpu = cpu1 = None
+    if not args.no_cpu_baseline and world == 1:     # the CPU baseline is an N=1 figure (rank 0)
+        cpu = cpu_baseline(args.batch, args.cpu_seconds, args.arch)
+        cpu1 = cpu_baseline(args.batch, args.cpu_seconds * 0.6, args.arch, threads=1)
+
+    step_roof = {"attainable_us": round(attain_us, 2), "step_us": round(ms * 1e3, 2),
+                 "frac": round(attain_us / (ms * 1e3), 4),
+                 "mfma_frac": round(step_flops / (ms * 1e-3) / (peak_tf * 1e12), 4),
+                 "step_gflop": round(step_flops / 1e9, 3)}
+    # the whole step's counter traffic against its algorithmic bytes (SURVEY §8(d))
+    step_bytes = sum(r[3] for r in rows)
+    st_tr, why_st = step_traffic([call_kernels(f_, r_) for (_, f_, _, _), r_ in zip(rows, rows_ref)], digest, args.arch, args.batch)
+    step_roof["algorithmic_bytes"] = int(step_bytes)
+    step_roof["traffic"] = st_tr["bytes"] if st_tr else None
+    step_roof["traffic_ratio"] = round(st_tr["bytes"] / step_bytes, 3) if st_tr and step_bytes else None
+    step_roof["traffic_source"] = st_tr["file"] if st_tr else {"missing": why_st}
+    dropin = dropin_eager = None
+    if world == 1 and not args.no_dropin and args.arch not in AE_WIDTHS:
+        dropin = dropin_leg(args, dtype, steps=max(20, min(args.steps, 100)))
+        dropin_eager = dropin_leg(args, dtype, engine="eager")
+    return {"sum_kernel_us_isolated": round(step_kernel_us, 1), "roofline": roof, "step_roofline": step_roof,
+            "dropin": dropin, "dropin_eager": dropin_eager, "cpu_baseline": cpu, "cpu_baseline_1thread": cpu1}
+
+
 def main():
     args = parse()
     if "RANK" not in os.environ and args.gpus > 1:
@@ -650,9 +775,23 @@ def main():
     if hasattr(plan, "eps") and not ae and not step.device_eps:
         plan.eps.copy_(torch.randn(plan.eps.shape, generator=g, device="cuda"))
 
+    # --dump-outputs: the training state every run starts from (seeded), kept for the dumped step
+    state = [net.params, net.running, opt.m, opt.v, opt.step] + ([plan.num_iter] if hasattr(plan, "num_iter") else [])
+    start = [t.clone() for t in state] if args.dump_outputs else None
     elapsed = timed_loop(step, args, distributed, torch.cuda.synchronize)
     loss_terms = step.loss_terms()                  # rank mean (sync_dist) when distributed
     finite = all(math.isfinite(v) for v in loss_terms)
+    if start is not None:
+        # the timed step once more (the same graph replay), from the seeded start state: K + W
+        # optimizer steps of this workload amplify the rounding of the bf16 step's float atomics
+        # (BatchNorm statistics) to differences of order one, so the state the timed steps end in
+        # is no basis for comparing two runs; one step from identical state and inputs is
+        for t, t0 in zip(state, start):
+            t.copy_(t0)
+        net.sync_lowp()
+        step()
+        torch.cuda.synchronize()
+        dump_terms = step.loss_terms()
 
     if rank != 0:
         if distributed:
@@ -660,78 +799,12 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- dominant kernel: per-launch time with HIP events on the step's stream
-    times = time_kernels(plan)
-    costs = kernel_costs(plan, dsz)
-    rows, rows_ref = [], []
-    for (fn, ref, us), (_, _, fl, by) in zip(times, costs):
-        rows.append((us, fn, fl, by))
-        rows_ref.append(ref)
-    if args.kernel_breakdown:
-        for us, fn, fl, by in rows:
-            print(f"{fn:28s} {us:9.2f} us  {fl / 1e9:8.3f} GF  {by / 1e6:8.2f} MB  "
-                  f"{(fl / us / 1e6) if us else 0:8.1f} TF/s  {(by / us / 1e3) if us else 0:8.1f} GB/s",
-                  file=sys.stderr)
-    idx = max(range(len(rows)), key=lambda i: rows[i][0])
-    us, fn, fl, by = rows[idx]
-    ai = fl / by if by else 0.0
-    peak_tf = MFMA_PEAK_TFLOPS[args.dtype]
-    ridge = peak_tf * 1e12 / (HBM_PEAK_GBS * 1e9)
-    if ai >= ridge:
-        roof = {"bound": "mfma", "achieved": round(fl / (us * 1e-6) / 1e12, 3), "peak": peak_tf, "unit": "TFLOP/s"}
-    else:
-        roof = {"bound": "hbm", "achieved": round(by / (us * 1e-6) / 1e9, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s"}
-    roof["frac"] = round(roof["achieved"] / roof["peak"], 4)
-    from vae_amd import _lib as L
-    digest = L.load().vae_build_digest().decode()
-    kernels = call_kernels(fn, rows_ref[idx])
-    tr, why_tr = pmc_traffic(kernels, digest, args.arch, args.batch)
-    roof["traffic"] = tr["bytes"] if tr else None
-    roof["traffic_ratio"] = round(tr["bytes"] / by, 3) if tr and by else None
-    roof["traffic_source"] = tr if tr else {"missing": why_tr}
-    roof["kernel"] = f"{fn} (call #{idx} of the step; its kernels: {', '.join(k[1] for k in kernels) or 'n/a'})"
-    roof["us_per_launch"] = round(us, 2)
-    rp, why_rp = rocprof_times(kernels, digest, args.arch, args.batch)
-    if rp and abs(rp["sum_avg_us"] - us) > PAIR_TOL * us:
-        # the profile's kernels do not account for this call's measured time: not the same work
-        # (another plan or launch count), so neither its times nor its counters are evidence here
-        why = (f"{rp['file']}: rocprof sum {rp['sum_avg_us']} us vs {us:.2f} us event time "
-               f"(> {PAIR_TOL:.0%} apart)")
-        rp, why_rp = None, why
-        roof["traffic"] = roof["traffic_ratio"] = None
-        roof["traffic_source"] = {"missing": why}
-    roof["rocprof"] = rp if rp else {"missing": why_rp}
-    roof["build_digest"] = digest
-    roof["algorithmic"] = {"flops": fl, "bytes": by, "ai_flop_per_byte": round(ai, 1)}
-    step_kernel_us = sum(r[0] for r in rows)
-    # the step-level attainable time — every kernel at its own roofline bound,
-    # max(flops / MFMA peak, bytes / HBM peak), summed — over the measured step time; and the
-    # literal MFMA fraction, all of the step's flops over the measured step at the bf16/fp32 peak
-    attain_us = sum(max(fl_ / (peak_tf * 1e6), by_ / (HBM_PEAK_GBS * 1e3)) for _, _, fl_, by_ in rows)
-    step_flops = sum(r[2] for r in rows)
-
-    cpu = cpu1 = None
-    if not args.no_cpu_baseline and world == 1:     # the CPU baseline is an N=1 figure (rank 0)
-        cpu = cpu_baseline(args.batch, args.cpu_seconds, args.arch)
-        cpu1 = cpu_baseline(args.batch, args.cpu_seconds * 0.6, args.arch, threads=1)
-
     ms = elapsed / args.steps * 1e3
     value = world * args.batch * args.steps / elapsed
-    step_roof = {"attainable_us": round(attain_us, 2), "step_us": round(ms * 1e3, 2),
-                 "frac": round(attain_us / (ms * 1e3), 4),
-                 "mfma_frac": round(step_flops / (ms * 1e-3) / (peak_tf * 1e12), 4),
-                 "step_gflop": round(step_flops / 1e9, 3)}
-    # the whole step's counter traffic against its algorithmic bytes
-    step_bytes = sum(r[3] for r in rows)
-    st_tr, why_st = step_traffic([call_kernels(f_, r_) for (_, f_, _, _), r_ in zip(rows, rows_ref)], digest, args.arch, args.batch)
-    step_roof["algorithmic_bytes"] = int(step_bytes)
-    step_roof["traffic"] = st_tr["bytes"] if st_tr else None
-    step_roof["traffic_ratio"] = round(st_tr["bytes"] / step_bytes, 3) if st_tr and step_bytes else None
-    step_roof["traffic_source"] = st_tr["file"] if st_tr else {"missing": why_st}
-    dropin = dropin_eager = None
-    if world == 1 and not args.no_dropin and args.arch not in AE_WIDTHS:
-        dropin = dropin_leg(args, dtype, steps=max(20, min(args.steps, 100)))
-        dropin_eager = dropin_leg(args, dtype, engine="eager")
+    if args.dump_outputs:                           # before --full's per-call timing reruns the kernels
+        dump_outputs(args.dump_outputs, {"loss_terms": torch.tensor(dump_terms, dtype=torch.float64),
+                                         "recon": plan.recon, "grads": plan.grads, "bn_running": net.running})
+    full = full_report(args, plan, dtype, dsz, world, ms) if args.full else {}
     line = {
         "metric": METRIC if args.arch == "vanilla" else f"train images/sec {args.arch} 64x64 bs={args.batch} (1 GPU config)",
         "value": round(value, 1),
@@ -765,13 +838,7 @@ def main():
                  if args.arch in AE_WIDTHS else      # (the Autoencoder's loss is the MSE alone)
                  {"loss": loss_terms[0], "Reconstruction_Loss": loss_terms[1],
                   ("VQ_Loss" if args.arch == "vq" else "KLD"): loss_terms[2], "finite": finite}),
-        "sum_kernel_us_isolated": round(step_kernel_us, 1),
-        "roofline": roof,
-        "step_roofline": step_roof,
-        "dropin": dropin,
-        "dropin_eager": dropin_eager,
-        "cpu_baseline": cpu,
-        "cpu_baseline_1thread": cpu1,
+        **full,
     }
     print(json.dumps(line), flush=True)
     if distributed:

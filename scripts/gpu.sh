@@ -9,7 +9,7 @@
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   tenv:V=x,W=y:EXPR  pytest -m gpu -k EXPR with environment overrides
 #   smoke            __graft_entry__.smoke()
-#   bench            default bench line (driver's command: N=1, CPU baseline included)
+#   bench            the whole bench line (bench.py --full: N=1, rooflines, drop-in legs, CPU baseline)
 #   quick            VanillaVAE bench, 200 steps, no CPU baseline, per-call breakdown
 #   qenv:V=x,W=y     the quick bench with environment overrides (tunable sweeps)
 #   aenv:V=x:A:B     the same as arch:A:B with environment overrides
@@ -47,7 +47,7 @@ run() {   # name seconds cmd...
 prof() {  # name bench-args...
   local name=$1; shift
   (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-     -d $O/${TAG}_${name} -o run -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin "$@") \
+     -d $O/${TAG}_${name} -o run -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-dropin "$@") \
      > $O/${TAG}_${name}.log 2>&1 || return $?
   cd $R && python3 tools/prof_summary.py --dir $O/${TAG}_${name} --out $O/${TAG}_${name}_kstats.json \
      --config "bench.py --steps 20 --warmup 5 $*" >> $O/${TAG}_${name}.log 2>&1
@@ -56,7 +56,7 @@ prof() {  # name bench-args...
 pmc() {   # name bench-args...   (one counter group per run: rocprofv3 does not split passes)
   # the graph-replayed step (the timed one); PMCNOGRAPH=1 profiles the eager launch sequence
   local name=$1; shift
-  local B="python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dropin ${PMCNOGRAPH:+--no-graph} $*"
+  local B="python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-dropin ${PMCNOGRAPH:+--no-graph} $*"
   cd /tmp && export TMPDIR=/tmp
   timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $O/${TAG}_${name}_pa -o run -- $B > $O/${TAG}_${name}_pa.log 2>&1 || return $?
   timeout -s KILL 120 rocprofv3 --pmc GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16 FETCH_SIZE --output-format csv -d $O/${TAG}_${name}_pb -o run -- $B > $O/${TAG}_${name}_pb.log 2>&1 || return $?
@@ -71,12 +71,12 @@ for step in "$@"; do
     tests) if [ -n "$a1" ]; then run tests_${a1//[^A-Za-z0-9]/_} 900 $PT -k "$a1"; else run tests 900 $PT; fi ;;
     tenv) run tenv_${a1//[=,]/_} 900 env ${a1//,/ } $PT -k "$a2" ;;
     smoke) run smoke 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python3 -u bench.py ;;
-    quick) run quick 300 python3 -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --kernel-breakdown ;;
-    qenv) run qenv_${a1//[=,]/_} 300 env ${a1//,/ } python3 -u bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-dropin ;;
-    aenv) run aenv_${a1//[=,]/_}_${a2}_${a3} 300 env ${a1//,/ } python3 -u bench.py --arch $a2 --batch $a3 --steps 100 --warmup 10 --no-cpu-baseline ;;
-    arch) run arch_${a1}_${a2} 300 python3 -u bench.py --arch $a1 --batch $a2 --steps 100 --warmup 10 --no-cpu-baseline --kernel-breakdown ;;
-    archcpu) run archcpu_${a1}_${a2} 400 python3 -u bench.py --arch $a1 --batch $a2 --steps 100 --warmup 10 --kernel-breakdown ;;
+    bench) run bench 400 python3 -u bench.py --full ;;
+    quick) run quick 300 python3 -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --kernel-breakdown ;;
+    qenv) run qenv_${a1//[=,]/_} 300 env ${a1//,/ } python3 -u bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-dropin ;;
+    aenv) run aenv_${a1//[=,]/_}_${a2}_${a3} 300 env ${a1//,/ } python3 -u bench.py --full --arch $a2 --batch $a3 --steps 100 --warmup 10 --no-cpu-baseline ;;
+    arch) run arch_${a1}_${a2} 300 python3 -u bench.py --full --arch $a1 --batch $a2 --steps 100 --warmup 10 --no-cpu-baseline --kernel-breakdown ;;
+    archcpu) run archcpu_${a1}_${a2} 400 python3 -u bench.py --full --arch $a1 --batch $a2 --steps 100 --warmup 10 --kernel-breakdown ;;
     prof) if [ -n "$a1" ]; then prof prof_$a1 --arch $a1 --batch $a2; else prof prof; fi ;;
     pmc) if [ -n "$a1" ]; then pmc pmc_$a1 --arch $a1 --batch $a2; else pmc pmc; fi ;;
     headbench) run headbench 200 python3 -u tools/headbench.py ;;

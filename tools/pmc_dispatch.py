@@ -47,7 +47,7 @@ def main():
     ap.add_argument("--dedupe", action="store_true")
     a = ap.parse_args()
     rows = [r for r in load(a.dir) if a.kernel in r["name"]]
-    if a.dedupe:       # bench.py times each call 20x back to back after the step: keep one of each run
+    if a.dedupe:       # bench.py --full times each call 20x back to back after the step: keep one of each run
         out = []
         for r in rows:
             if out and out[-1]["name"] == r["name"] and out[-1]["grid"] == r["grid"]:

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Per-launch kernel durations from a rocprofv3 kernel trace of `bench.py` (diagnostic).
+"""Per-launch kernel durations from a rocprofv3 kernel trace of `bench.py --full` (diagnostic).
 
-bench.py's time_kernels() queues every C-ABI call of the step behind a spin kernel, 20 times.
+bench.py's time_kernels() (a leg of --full) queues every C-ABI call of the step behind a spin kernel, 20 times.
 This groups the trace into (spin, kernels of one call) segments and prints, per call of the
 step, the median duration of each kernel it launched and the gap to the next kernel.
 
