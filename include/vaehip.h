@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAE_ABI_VERSION 25
+#define VAE_ABI_VERSION 26
 
 enum vae_dtype { VAE_F32 = 0, VAE_BF16 = 1 };
 
@@ -254,9 +254,10 @@ typedef struct vae_head_args {
 
 
 
-/* Loss kinds (vanilla_vae.py:124-146, beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211) */
+/* Loss kinds (vanilla_vae.py:124-146, beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211,
+ * info_vae.py:128-148) */
 enum vae_loss_kind { VAE_LOSS_VANILLA = 0, VAE_LOSS_BETA_H = 1, VAE_LOSS_BETA_B = 2, VAE_LOSS_IWAE = 3,
-                     VAE_LOSS_VQ = 4 };
+                     VAE_LOSS_VQ = 4, VAE_LOSS_INFO = 5 };
 
 typedef struct vae_elbo_args {
   int32_t kind;            /* vae_loss_kind */
@@ -277,7 +278,59 @@ typedef struct vae_elbo_args {
   const float* vq_sse;     /* [1] Σ(q - latents)^2 written by vae_vq_fwd */
   float vq_beta;
   float vq_elems;          /* number of latent elements (N*H*W*D) */
+  /* VAE_LOSS_INFO (InfoVAE, info_vae.py:128-148; one sample):
+   *   loss = recon_weight*recon + kl_factor*kld_weight*kld + mmd_coef*mmd, with the caller's
+   *   recon_weight = beta, kl_factor = 1 - alpha, mmd_coef = (alpha + reg_weight - 1)/(B(B-1));
+   *   mmd = sum over t < mmd_tiles, in ascending order, of the vae_mmd partials
+   *   (pp_t + zz_t - 2 pz_t; doubles, 4 per tile);
+   *   head_coef = recon_weight*2/(B*img_elems), kl_coef = kl_factor*kld_weight/B;
+   *   out = {loss, Reconstruction_Loss, -kld (as the reference reports it), kld}, mmd_out[0] = mmd. */
+  float recon_weight, kl_factor, mmd_coef;
+  int32_t mmd_tiles;
+  const double* mmd_partials;
+  float* mmd_out;          /* [1] */
 } vae_elbo_args;
+
+/* Maximum mean discrepancy between the batch of latents and a prior sample, and its gradient
+ * (InfoVAE.compute_mmd, info_vae.py:150-229; the same term WAE-MMD uses).
+ *   z = mu + eps*exp(log_var/2) is recomputed in fp32 from mulv / eps (never read from a bf16 z).
+ *   VAE_MMD_IMQ: C = 2*latent*latent_var, k(a,b) = C/(1e-7 + C + |a-b|^2); each of the three terms is
+ *     the sum over i != j of k — the reference drops the diagonal of the prior-vs-z matrix too and its
+ *     .mean() of that scalar is a no-op;  mmd = S_pp + S_zz - 2 S_pz.
+ *   VAE_MMD_RBF: k = exp(-mean_d((a-b)^2)/(2*latent*latent_var)); each term is the mean over all
+ *     B^2 entries, diagonal included.
+ *   dz [batch][latent] = grad_scale * dmmd/dz; with dmulv set the reparameterization backward of dz
+ *   is added to it (dmu += dz, dlog_var += dz*0.5*eps*exp(log_var/2)).
+ *   prior_gen = 0: `prior` [batch][latent] is read.  prior_gen = 1: prior ~ N(0,1) is DRAWN
+ *   (torch.randn_like(z), info_vae.py:220) and written to `prior`: Philox4x32-10 + Box-Muller keyed by
+ *   prior_seed, counter (element/4, *prior_step, 0x9A1D, 0) — the generator of
+ *   vae_latent_args.eps_gen on another stream word, so a captured step draws a fresh prior, independent
+ *   of its eps, on every replay.
+ * One launch: a workgroup owns 16 latent rows and the 16 prior rows of the same indices, streams every
+ * row of [z; prior] through LDS, and forms both products (pairwise dot products, then weights x rows
+ * for the gradient) on v_mfma_f32_16x16x4_f32; d^2 = |a|^2 + |b|^2 - 2 a.b clamped at 0, the diagonal
+ * of the same-set matrices taken out by index.  Its three partial sums go to the workspace as doubles
+ * [tiles][4] = {pp, zz, pz, 0} (rbf: already divided by B^2) for vae_elbo_fwd (VAE_LOSS_INFO) to add
+ * in tile order: no float atomics, so repeated calls are bit-identical.
+ * Shapes: 2 <= batch <= 1024 (VAE_E_BADSHAPE below 2: the reference divides by B(B-1)),
+ * latent % 32 == 0, latent <= 256. */
+enum vae_mmd_kind { VAE_MMD_IMQ = 0, VAE_MMD_RBF = 1 };
+typedef struct vae_mmd_args {
+  int32_t kind;            /* vae_mmd_kind */
+  int32_t batch, latent;
+  float latent_var;
+  float grad_scale;
+  int32_t prior_gen;
+  const float* mulv;       /* [batch][2*latent] */
+  const float* eps;        /* [batch][latent] */
+  float* prior;            /* [batch][latent]: read (prior_gen 0) or written (prior_gen 1) */
+  float* dz;               /* [batch][latent] out */
+  float* dmulv;            /* [batch][2*latent] accumulated, or NULL */
+  void* workspace;         /* vae_mmd_workspace_size bytes: the partials, 8-byte aligned */
+  int64_t workspace_bytes;
+  const int32_t* prior_step;
+  uint64_t prior_seed;
+} vae_mmd_args;
 
 /* VectorQuantizer (models/vq_vae.py:24-55) on NHWC latents [rows][dim] (rows = N*H*W, the
  * reference's flat_latents after its permute, :25-27) against the fp32 codebook [codes][dim].
@@ -397,6 +450,16 @@ int vae_pad_channels(int32_t dtype, int64_t rows, int32_t c, int32_t cp, const v
 int vae_unpad_accumulate(int64_t rows, int32_t cp, int32_t c, const float* src, float* dst, void* stream);
 /* --- ELBO terms + backward seeds (vanilla_vae.py:124-146 and variants) -------------- */
 int vae_elbo_fwd(const vae_elbo_args* a, void* stream);
+/* --- MMD of the latents against a prior sample + its gradient (info_vae.py:150-229), see
+ *     vae_mmd_args.  vae_mmd_workspace_size: bytes of partials (host only; *tiles, if set, gets the
+ *     tile count vae_elbo_args.mmd_tiles takes).
+ *     vae_mmd_reseed: dmulv += reparameterization backward of (*scale) * dz for a dz that vae_mmd
+ *     stored (grad_scale 1 there): the seed of a backward whose dL/dloss is only known later or that
+ *     runs again (the drop-in loss_function path). */
+int vae_mmd_fwd(const vae_mmd_args* a, void* stream);
+int vae_mmd_workspace_size(const vae_mmd_args* a, size_t* bytes, int32_t* tiles);
+int vae_mmd_reseed(int32_t batch, int32_t latent, const float* dz, const float* scale, const float* mulv,
+                   const float* eps, float* dmulv, void* stream);
 /* --- Adam (experiment.py:308-311; torch.optim.Adam semantics), flat fp32 buffers.
  *     step/lr are device scalars so the call can be replayed from a graph.  When
  *     p_lowp != NULL the updated parameters are also written as bf16 (weight copies). --- */

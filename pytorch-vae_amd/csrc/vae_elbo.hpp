@@ -1,5 +1,5 @@
 // ELBO of the VAE family on one workgroup (vaehip.h vae_elbo_fwd; vanilla_vae.py:124-146,
-// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211).
+// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211, info_vae.py:128-148).
 #pragma once
 #include "vae_common.hpp"
 
@@ -52,8 +52,22 @@ __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_ro
   if (a.kind != VAE_LOSS_IWAE) {
     const float recon = sse_tot / ((float)B * (float)a.img_elems);
     float loss, klc, kld_report;
+    float rw = 1.f;                               // weight of the reconstruction term (and its seed)
     if (a.kind == VAE_LOSS_VANILLA) {
       loss = recon + a.kld_weight * kld_mean; klc = a.kld_weight; kld_report = -kld_mean;
+    } else if (a.kind == VAE_LOSS_INFO) {
+      // info_vae.py:141-148: the MMD term is the vae_mmd partials added in tile order (doubles, so
+      // S_pp + S_zz - 2 S_pz keeps its digits through the cancellation); every thread adds them
+      double pp = 0.0, zz = 0.0, pz = 0.0;
+      for (int t = 0; t < a.mmd_tiles; ++t) {
+        pp += a.mmd_partials[4 * t]; zz += a.mmd_partials[4 * t + 1]; pz += a.mmd_partials[4 * t + 2];
+      }
+      const float mmd = (float)(pp + zz - 2.0 * pz);
+      rw = a.recon_weight;
+      klc = a.kl_factor * a.kld_weight;
+      loss = rw * recon + klc * kld_mean + a.mmd_coef * mmd;
+      kld_report = -kld_mean;
+      if (threadIdx.x == 0) a.mmd_out[0] = mmd;
     } else if (a.kind == VAE_LOSS_BETA_H) {
       loss = recon + a.beta * a.kld_weight * kld_mean; klc = a.beta * a.kld_weight; kld_report = kld_mean;
     } else {
@@ -64,7 +78,7 @@ __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_ro
       klc = a.gamma * a.kld_weight * (dlt > 0.f ? 1.f : (dlt < 0.f ? -1.f : 0.f));
       kld_report = kld_mean;
     }
-    const float hc = 2.f / ((float)B * (float)a.img_elems);
+    const float hc = rw * 2.f / ((float)B * (float)a.img_elems);
     for (int i = threadIdx.x; i < B; i += 256) { a.head_coef[i] = hc; a.kl_coef[i] = klc / (float)B; }
     if (threadIdx.x == 0) { a.out[0] = loss; a.out[1] = recon; a.out[2] = kld_report; a.out[3] = kld_mean; }
     return;

@@ -819,7 +819,11 @@ extern "C" int vae_reparam_fwd(int32_t dtype, int32_t rows, int32_t samples, int
 
 extern "C" int vae_elbo_fwd(const vae_elbo_args* a, void* stream) {
   if (!a || !a->sse || !a->out || !a->per_img) return fail(VAE_E_BADARG, "elbo_fwd: args");
-  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_VQ) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_INFO) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind == VAE_LOSS_INFO) {
+    if (!a->mmd_partials || !a->mmd_out || a->mmd_tiles <= 0) return fail(VAE_E_BADARG, "elbo_fwd: mmd partials / mmd_out");
+    if (a->batch < 2 || a->samples > 1) return fail(VAE_E_BADSHAPE, "elbo_fwd: InfoVAE needs batch >= 2, one sample");
+  }
   if (a->kind == VAE_LOSS_VQ) {
     if (!a->vq_sse || !(a->vq_elems > 0.f)) return fail(VAE_E_BADARG, "elbo_fwd: vq_sse / vq_elems");
     if (a->batch <= 0 || a->img_elems <= 0 || (a->samples > 1)) return fail(VAE_E_BADSHAPE, "elbo_fwd: sizes");

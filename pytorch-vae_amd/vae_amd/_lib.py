@@ -19,11 +19,12 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 # any other value V loads libvaehip_V.so (a build-flag variant for A/B timing)
 if os.environ.get("VAE_HIP_LIB"):
     LIB_PATH = LIB_PATH.replace("libvaehip.so", "libvaehip_%s.so" % os.environ["VAE_HIP_LIB"])
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 F32, BF16 = 0, 1
 X_NONE, X_ACT, X_BN_ACT, X_BN_DY = 0, 1, 2, 3
-LOSS_VANILLA, LOSS_BETA_H, LOSS_BETA_B, LOSS_IWAE, LOSS_VQ = 0, 1, 2, 3, 4
+LOSS_VANILLA, LOSS_BETA_H, LOSS_BETA_B, LOSS_IWAE, LOSS_VQ, LOSS_INFO = 0, 1, 2, 3, 4, 5
+MMD_IMQ, MMD_RBF = 0, 1                                          # vaehip.h enum vae_mmd_kind
 
 
 class VaeHipError(RuntimeError):
@@ -87,7 +88,17 @@ class ElboArgs(ctypes.Structure):
                 ("img_elems", c_int32), ("kld_weight", c_float), ("beta", c_float), ("gamma", c_float),
                 ("c_max", c_float), ("c_stop_iter", c_float), ("iter", c_void_p), ("mulv", c_void_p),
                 ("sse", c_void_p), ("out", c_void_p), ("per_img", c_void_p), ("head_coef", c_void_p),
-                ("kl_coef", c_void_p), ("vq_sse", c_void_p), ("vq_beta", c_float), ("vq_elems", c_float)]
+                ("kl_coef", c_void_p), ("vq_sse", c_void_p), ("vq_beta", c_float), ("vq_elems", c_float),
+                ("recon_weight", c_float), ("kl_factor", c_float), ("mmd_coef", c_float), ("mmd_tiles", c_int32),
+                ("mmd_partials", c_void_p), ("mmd_out", c_void_p)]
+
+
+class MmdArgs(ctypes.Structure):
+    """vaehip.h vae_mmd_args (MMD of the latents against a prior sample + its gradient)."""
+    _fields_ = [("kind", c_int32), ("batch", c_int32), ("latent", c_int32), ("latent_var", c_float),
+                ("grad_scale", c_float), ("prior_gen", c_int32), ("mulv", c_void_p), ("eps", c_void_p),
+                ("prior", c_void_p), ("dz", c_void_p), ("dmulv", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_int64), ("prior_step", c_void_p), ("prior_seed", ctypes.c_uint64)]
 
 
 SLAB_MAX = 32                      # vaehip.h VAE_SLAB_MAX
@@ -205,6 +216,9 @@ _SIGS = {
     "vae_bn_finalize": [POINTER(BnArgs), c_void_p],
     "vae_reparam_fwd": [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p],
     "vae_elbo_fwd": [POINTER(ElboArgs), c_void_p],
+    "vae_mmd_fwd": [POINTER(MmdArgs), c_void_p],
+    "vae_mmd_workspace_size": [POINTER(MmdArgs), POINTER(ctypes.c_size_t), POINTER(c_int32)],
+    "vae_mmd_reseed": [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "vae_vq_fwd": [POINTER(VqArgs), c_void_p],
     "vae_vq_bwd": [POINTER(VqArgs), c_void_p],
     "vae_recon_fwd": [POINTER(ReconArgs), c_void_p],
@@ -384,6 +398,13 @@ def recon_loss_args(kind: int, n: int, c: int, h: int, w: int, *, mask=None, win
             a.level_weights[i] = float(v)
         a.normalize = int(normalize)
     return a
+
+
+def mmd_workspace(a: "MmdArgs"):
+    """(bytes of partials, tile count) of a vae_mmd_fwd call (vae_mmd_workspace_size; no device)."""
+    out, tiles = ctypes.c_size_t(0), c_int32(0)
+    call("vae_mmd_workspace_size", ctypes.byref(a), ctypes.byref(out), ctypes.byref(tiles))
+    return int(out.value), int(tiles.value)
 
 
 def recon_loss_workspace(a: "ReconLossArgs") -> int:

@@ -125,12 +125,17 @@ class TrainStep:
     def __init__(self, net, plan, opt: FusedAdam, *, graph: bool = True, process_group=None,
                  nbuckets: int = 2, device_eps: Optional[int] = None, force_buckets: bool = False,
                  graph_comm: bool = True, begin_ex: bool = True, defer_reductions: bool = True,
-                 overlap: bool = True, comm_dtype: torch.dtype = torch.float32, split_adam: bool = True):
+                 overlap: bool = True, comm_dtype: torch.dtype = torch.float32, split_adam: bool = True,
+                 device_prior: Optional[int] = None):
         self.net, self.plan, self.opt = net, plan, opt
         # device_eps = seed: the forward draws eps itself every step (StepPlan.use_device_eps, keyed
         # by the optimizer's step counter) — the reference's per-step randn_like inside the step
         self.device_eps = (device_eps is not None and hasattr(plan, "use_device_eps")
                            and plan.use_device_eps(opt.step, device_eps))
+        # device_prior = seed (InfoVAE): the MMD kernel draws its prior sample itself every step
+        # (StepPlan.use_device_prior; info_vae.py:220's randn_like), keyed by the same step counter
+        self.device_prior = (device_prior is not None and hasattr(plan, "use_device_prior")
+                             and plan.use_device_prior(opt.step, device_prior))
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.use_graph = graph
@@ -240,6 +245,10 @@ class TrainStep:
             p._run(p.fwd_calls[skip:], st)
             if self.comm is not None and not getattr(p, "elbo_in_head", False):
                 p.metrics.copy_(p.out)
+                if p.loss_kind == L.LOSS_INFO:
+                    # the fourth logged term of an InfoVAE step (each rank's MMD is over its own
+                    # shard, as under the reference's DDP; the all-reduce makes it the rank mean)
+                    p.metrics[3:4].copy_(p.mmd)
         lo = 0 if k == 0 else self.buckets[k - 1][0]
         if self.deferred:
             L.call("vae_deferred_reset")
@@ -421,3 +430,10 @@ class TrainStep:
         """[loss, Reconstruction_Loss, KLD|VQ_Loss] of the last step: the mean over ranks with more
         than one (what the reference logs, experiment.py:55), else this rank's."""
         return (self.plan.metrics if self.comm is not None else self.plan.out)[:3].tolist()
+
+    def mmd_term(self) -> float:
+        """InfoVAE: the 'MMD' entry of the last step's loss dict (info_vae.py:148), the mean over ranks
+        with more than one."""
+        if self.plan.loss_kind != L.LOSS_INFO:
+            raise ValueError("this step's loss has no MMD term")
+        return float(self.plan.metrics[3] if self.comm is not None else self.plan.mmd)

@@ -262,6 +262,9 @@ class GraphedSteps:
             # so manual_seed still fixes the run) where the fused bottleneck can; else plan.eps below
             if hasattr(step.plan, "use_device_eps") and not getattr(step, "zero_eps", False):
                 step.device_eps = step.plan.use_device_eps(self.fused.step, int(torch.randint(0, 2 ** 62, (1,))))
+            # InfoVAE: the prior sample of its MMD term drawn the same way, inside vae_mmd_fwd
+            if getattr(step.plan, "prior", None) is not None:
+                step.device_prior = step.plan.use_device_prior(self.fused.step, int(torch.randint(0, 2 ** 62, (1,))))
         lr = self.opt.param_groups[0]['lr']
         if lr != self._lr:                            # (a device scalar: written only on change)
             self.fused.set_lr(lr)
@@ -271,6 +274,8 @@ class GraphedSteps:
         plan = step.plan
         if hasattr(plan, "eps") and not getattr(step, "zero_eps", False) and not getattr(step, "device_eps", False):
             plan.eps.normal_()                        # torch.randn_like(std), vanilla_vae.py:116
+        if getattr(plan, "prior", None) is not None and not getattr(step, "device_prior", False):
+            plan.prior.normal_()                      # torch.randn_like(z), info_vae.py:220
         step(imgs)
         self.nstep += 1
         self.opt.state[model.flat]['step'] = torch.tensor(float(self.nstep))
@@ -293,9 +298,12 @@ class GraphedSteps:
         if self._ext is None:
             ie = plan.x[0].numel()
             third = "VQ_Loss" if not hasattr(plan, "eps") else "KLD"
-            self._terms_buf = torch.zeros(3, device=dev)
+            info = getattr(plan, "prior", None) is not None                     # InfoVAE: a fourth term
+            self._terms_buf = torch.zeros(4 if info else 3, device=dev)
             self._terms = {'loss': self._terms_buf[0], 'Reconstruction_Loss': self._terms_buf[1],
                            third: self._terms_buf[2]}
+            if info:
+                self._terms['MMD'] = self._terms_buf[3]
             if getattr(step, "zero_eps", False):                                # Autoencoder
                 z = torch.zeros((), device=dev)
                 self._terms.update(KLD=z, feature_loss=z)
@@ -316,6 +324,8 @@ class GraphedSteps:
         a.hi_img, a.lo_img = e['img'][0].data_ptr(), e['img'][1].data_ptr()
         a.hi_recon, a.lo_recon = e['recon'][0].data_ptr(), e['recon'][1].data_ptr()
         L.call("vae_step_record", ctypes.byref(a), L.stream_ptr())
+        if 'MMD' in self._terms:           # info_vae.py:148 (with more ranks: the rank mean, metrics[3])
+            self._terms_buf[3:4].copy_(plan.metrics[3:4] if step.world > 1 else plan.mmd)
         self._per.append((self._per_off, B))
         self._per_off += B
 

@@ -6,6 +6,7 @@ Mirrors the reference interface (paths relative to the reference root):
   VanillaVAE              models/vanilla_vae.py:8-173
   BetaVAE                 models/beta_vae.py:8-179  (loss_type 'H' / 'B', per-instance num_iter)
   IWAE                    models/iwae.py:8-188      (num_samples; row-major b*S+s latent order)
+  InfoVAE                 models/info_vae.py:8-256  (MMD term on vae_mmd_fwd; imq / rbf kernels)
   VQVAE                   models/vq_vae.py:73-219   (VectorQuantizer, residual stacks; vae_amd/vq.py)
   vae_models registry     models/__init__.py:35-56
 
@@ -27,6 +28,7 @@ backward; model.eval(): eval-mode BatchNorm from the running statistics, forward
 from __future__ import annotations
 
 import math
+import warnings
 from abc import abstractmethod
 from typing import Any, Dict, List, Optional, Union
 
@@ -154,11 +156,18 @@ class _HipELBO(torch.autograd.Function):
         # the unscaled backward seeds of this loss (a repeated backward rescales from these)
         ctx.seeds = (plan.head_coef.clone(), plan.kl_coef.clone())
         loss, rl, kld = plan.out[0].clone(), plan.out[1].clone(), plan.out[2].clone()
+        # InfoVAE: a third seed, dmmd/dz (vae_mmd_fwd at run_elbo), applied scaled in the backward;
+        # the loss dict's MMD entry is a fourth output
+        ctx.mmd_seed = (plan.dz_mmd.clone(), plan.mmd_coef) if loss_kw["loss"] == "info" else None
+        if ctx.mmd_seed is not None:
+            mmd = plan.mmd[0].clone()
+            ctx.mark_non_differentiable(rl, kld, mmd)
+            return loss, rl, kld, mmd
         ctx.mark_non_differentiable(rl, kld)
         return loss, rl, kld
 
     @staticmethod
-    def backward(ctx, g_loss: Optional[Tensor], g_rl, g_kld):
+    def backward(ctx, g_loss: Optional[Tensor], g_rl, g_kld, g_mmd=None):
         plan = ctx.plan
         if g_loss is None:
             return None, None, None, None, None, None
@@ -167,6 +176,9 @@ class _HipELBO(torch.autograd.Function):
         plan.backward_done = True
         torch.mul(ctx.seeds[0], g_loss, out=plan.head_coef)
         torch.mul(ctx.seeds[1], g_loss, out=plan.kl_coef)
+        if ctx.mmd_seed is not None:
+            plan.dz_mmd.copy_(ctx.mmd_seed[0])
+            plan.seed_mmd(g_loss, ctx.mmd_seed[1], L.stream_ptr())
         plan.seed_fused(True)
         try:
             plan.backward(L.stream_ptr())
@@ -228,19 +240,22 @@ class _HipVAE(BaseVAE):
 
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
-                         plan_options: Optional[dict] = None):
+                         plan_options: Optional[dict] = None, device_eps: Optional[int] = None,
+                         device_prior: Optional[int] = None):
         """The whole training step of this model — forward, loss_function (vae_elbo_fwd), backward,
         [gradient all-reduce], Adam — as one engine.TrainStep on the model's own parameters,
         replayed from HIP graphs: the graph path of VAEXperiment.training_step + backward +
         optimizer.step (experiment.fit(..., engine="graph")).  `opt`: an engine.FusedAdam to share
         (one Adam state for the steps of every batch size, as the reference's single optimizer).
         `plan_options`: StepPlan route options (latent_kernels, head_kernels, pad_rgb, materialise,
-        mat_min_flops, batch_wgrads, wg_overlap)."""
+        mat_min_flops, batch_wgrads, wg_overlap).  `device_eps` / `device_prior`: seeds to draw eps (and
+        InfoVAE's prior sample) on the device inside the step (TrainStep)."""
         from .engine import FusedAdam, TrainStep
         plan = StepPlan(self.net, batch, kld_weight=kld_weight, **self._loss_config(), **(plan_options or {}))
         if opt is None:
             opt = FusedAdam(self.net, lr=lr, betas=betas, weight_decay=weight_decay)
-        return TrainStep(self.net, plan, opt, graph=graph, process_group=process_group)
+        return TrainStep(self.net, plan, opt, graph=graph, process_group=process_group, device_eps=device_eps,
+                         device_prior=device_prior)
 
     def _gpu_loss(self, args, loss: str, **kw):
         """The loss dict terms from vae_elbo_fwd when `args` are exactly what this model's last
@@ -260,9 +275,14 @@ class _HipVAE(BaseVAE):
         training = self.training if training is None else training
         key = (batch, training)
         if key not in self._plans:
-            self._plans[key] = StepPlan(self.net, batch, loss="iwae" if self.samples > 1 else "vanilla",
-                                        samples=self.samples, fused_loss=False, training=training)
+            self._plans[key] = StepPlan(self.net, batch, **self._dropin_config(), fused_loss=False,
+                                        training=training)
         return self._plans[key]
+
+    def _dropin_config(self) -> dict:
+        """StepPlan loss arguments of the drop-in plans (their loss is chosen at loss_function time;
+        the plan only has to hold what that loss needs)."""
+        return dict(loss="iwae" if self.samples > 1 else "vanilla", samples=self.samples)
 
     def _eval_forward(self, input: Tensor, eps: Optional[Tensor]):
         """model.eval() forward (no autograd): encoder, reparameterization, decoder with running
@@ -454,6 +474,97 @@ class IWAE(_HipVAE):
         weight = F.softmax(log_weight, dim=-1)
         loss = torch.mean(torch.sum(weight * log_weight, dim=-1), dim=0)
         return {'loss': loss, 'Reconstruction_Loss': log_p_x_z.mean(), 'KLD': -kld_loss.mean()}
+
+
+class InfoVAE(_HipVAE):
+    """models/info_vae.py:8-256 on libvaehip: the VanillaVAE network with the loss
+    beta * recon + (1 - alpha) * M_N * kld + (alpha + reg_weight - 1) / (B (B - 1)) * mmd, the MMD of the
+    batch's latents against a fresh prior sample on vae_mmd_fwd (imq or rbf kernel)."""
+
+    _warned_one_image = False          # (the one-image deviation of loss_function is announced once)
+
+    def __init__(self, in_channels: int, latent_dim: int, hidden_dims: List = None, alpha: float = -0.5,
+                 beta: float = 5.0, reg_weight: int = 100, kernel_type: str = 'imq', latent_var: float = 2.,
+                 **kwargs) -> None:
+        assert alpha <= 0, 'alpha must be negative or zero.'
+        super().__init__(in_channels, latent_dim, hidden_dims, **kwargs)
+        self.reg_weight = reg_weight
+        self.kernel_type = kernel_type
+        self.z_var = latent_var
+        self.alpha = alpha
+        self.beta = beta
+
+    def _loss_config(self) -> dict:
+        if self.kernel_type not in ('imq', 'rbf'):
+            raise ValueError('Undefined kernel type.')
+        return dict(loss="info", alpha=float(self.alpha), beta=float(self.beta), reg_weight=float(self.reg_weight),
+                    kernel_type=self.kernel_type, latent_var=float(self.z_var))
+
+    def _dropin_config(self) -> dict:
+        return self._loss_config()
+
+    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
+        """info_vae.py:123-126: [recons, input, z, mu, log_var]."""
+        recon, mu, log_var, eps = self._run(input, kwargs.get("eps"))
+        z = eps.reshape(mu.shape) * torch.exp(0.5 * log_var) + mu
+        out = [recon, input, z, mu, log_var]
+        if self.training and torch.is_grad_enabled() and recon.grad_fn is not None:
+            self._last = (self._plan(input.shape[0]), input, recon, mu, log_var, z)
+        else:
+            self._last = None
+        return out
+
+    def loss_function(self, *args, **kwargs) -> dict:
+        """info_vae.py:128-148.  `prior` (keyword, optional): the prior sample of compute_mmd in place
+        of a fresh torch.randn_like(z)."""
+        recons, input, z, mu, log_var = args[0], args[1], args[2], args[3], args[4]
+        kld_weight = kwargs['M_N']
+        prior = kwargs.get("prior")
+        if prior is None:
+            prior = torch.randn_like(z)
+        last = self._last
+        if (last is not None and self.training and torch.is_grad_enabled() and recons is last[2] and input is last[1]
+                and z is last[5] and mu is last[3] and log_var is last[4]):
+            g = _HipELBO.apply(self.flat, recons, mu, log_var, last[0],
+                               dict(loss="info", kld_weight=kld_weight, beta=float(self.beta), alpha=float(self.alpha),
+                                    reg_weight=float(self.reg_weight), prior=prior))
+            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'MMD': g[3], 'KLD': g[2]}
+        batch_size = input.size(0)
+        bias_corr = batch_size * (batch_size - 1)
+        recons_loss = F.mse_loss(recons, input)
+        mmd_loss = self.compute_mmd(z, prior)
+        kld_loss = torch.mean(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
+        loss = self.beta * recons_loss + (1. - self.alpha) * kld_weight * kld_loss
+        if bias_corr > 0:
+            loss = loss + (self.alpha + self.reg_weight - 1.) / bias_corr * mmd_loss
+        elif not InfoVAE._warned_one_image:
+            InfoVAE._warned_one_image = True
+            warnings.warn("InfoVAE.loss_function on a one-image batch: the MMD term (over no pairs; the "
+                          "reference divides by B(B-1) = 0) is left out of the loss", stacklevel=2)
+        # (one image — experiment.test_step scores images one by one: the reference divides by
+        # B(B-1) = 0 there and raises; the term, an MMD over no pairs, is left out instead)
+        return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'MMD': mmd_loss, 'KLD': -kld_loss}
+
+    def compute_kernel(self, x1: Tensor, x2: Tensor) -> Tensor:
+        """info_vae.py:150-216 (torch; the loss on foreign tensors / in eval mode)."""
+        D = x1.size(1)
+        x1 = x1.unsqueeze(-2)
+        x2 = x2.unsqueeze(-3)
+        if self.kernel_type == 'rbf':
+            sigma = 2. * D * self.z_var
+            return torch.exp(-((x1 - x2).pow(2).mean(-1) / sigma))
+        if self.kernel_type == 'imq':
+            C = 2 * D * self.z_var
+            kernel = C / (1e-7 + C + (x1 - x2).pow(2).sum(dim=-1))
+            return kernel.sum() - kernel.diag().sum()
+        raise ValueError('Undefined kernel type.')
+
+    def compute_mmd(self, z: Tensor, prior_z: Optional[Tensor] = None) -> Tensor:
+        """info_vae.py:218-229."""
+        if prior_z is None:
+            prior_z = torch.randn_like(z)
+        return (self.compute_kernel(prior_z, prior_z).mean() + self.compute_kernel(z, z).mean()
+                - 2 * self.compute_kernel(prior_z, z).mean())
 
 
 class MSSIM(nn.Module):
@@ -794,7 +905,8 @@ class VQVAE(BaseVAE):
 
 
 # models/__init__.py:35-56: the families on the MI355X path; the others raise on use.
-_ON_PATH = {'VanillaVAE': VanillaVAE, 'BetaVAE': BetaVAE, 'IWAE': IWAE, 'VQVAE': VQVAE, 'Autoencoder': Autoencoder}
+_ON_PATH = {'VanillaVAE': VanillaVAE, 'BetaVAE': BetaVAE, 'IWAE': IWAE, 'VQVAE': VQVAE, 'Autoencoder': Autoencoder,
+            'InfoVAE': InfoVAE}
 _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 'DIPVAE', 'BetaVAE', 'InfoVAE',
                     'WAE_MMD', 'VampVAE', 'GammaVAE', 'MSSIMVAE', 'JointVAE', 'BetaTCVAE', 'FactorVAE',
                     'LogCoshVAE', 'VanillaVAE', 'ConditionalVAE', 'CategoricalVAE', 'Autoencoder']
@@ -803,7 +915,7 @@ _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 
 def _not_on_path(name):
     def ctor(*args, **kwargs):
         raise NotImplementedError(f"{name} is not on the MI355X training path of this build "
-                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder are; DESIGN.md §7)")
+                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE are; DESIGN.md §7)")
     return ctor
 
 

@@ -126,7 +126,9 @@ class VAENet:
 class StepPlan:
     """All buffers and prebuilt launches of one training step for a fixed batch shape.
 
-    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae';  samples: IWAE S (decoder batch B*S).
+    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae' | 'info';  samples: IWAE S (decoder batch B*S).
+    'info' (InfoVAE, models/info_vae.py:128-229) takes alpha, beta, reg_weight, kernel_type and
+    latent_var; its MMD term runs on vae_mmd_fwd right after the reparameterization.
     grads land in `self.grads` (same layout as net.params); `zero` (grads, BN sums, SSE,
     d[mu|logvar]) is cleared by `vae_step_begin` at the start of every step."""
 
@@ -137,7 +139,8 @@ class StepPlan:
                  wg_overlap: bool = False, recon_loss: Optional[dict] = None,
                  deterministic: Optional[bool] = None, latent_kernels: bool = True, head_kernels: bool = True,
                  pad_rgb: bool = True, materialise: bool = True, mat_min_flops: float = MAT_MIN_FLOPS,
-                 batch_wgrads: bool = True):
+                 batch_wgrads: bool = True, alpha: float = -0.5, reg_weight: float = 100.0,
+                 kernel_type: str = "imq", latent_var: float = 2.0):
         # Route options (explicit arguments; every non-default route has a GPU test,
         # tests/test_gpu_routes.py): latent_kernels / head_kernels / pad_rgb / materialise /
         # batch_wgrads = False keep the generic per-op calls in place of the dedicated bottleneck
@@ -173,8 +176,15 @@ class StepPlan:
         self.bn_in_consumer = bn_in_consumer and training
         self.S = samples if loss == "iwae" else 1
         self.loss_kind = {"vanilla": L.LOSS_VANILLA, "betaH": L.LOSS_BETA_H, "betaB": L.LOSS_BETA_B,
-                          "iwae": L.LOSS_IWAE}[loss]
+                          "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO}[loss]
         self.kld_weight, self.beta, self.gamma = kld_weight, beta, gamma
+        if kernel_type not in MMD_KINDS:
+            raise ValueError('Undefined kernel type.')                   # info_vae.py:173
+        if loss == "info" and fused_loss and not training:
+            # an eval plan has no MMD call (nothing to seed), so the fused VAE_LOSS_INFO ELBO would
+            # find no partials: the loss of an eval forward is the caller's (models.InfoVAE)
+            raise ValueError("StepPlan(loss='info', training=False) has no fused loss: pass fused_loss=False")
+        self.alpha, self.reg_weight, self.kernel_type, self.latent_var = alpha, reg_weight, kernel_type, latent_var
         self.c_max, self.c_stop = max_capacity, capacity_max_iter
         dev, T = net.device, net.dtype
         D, h, img = net.latent_dim, net.hidden_dims, net.img_size
@@ -237,6 +247,14 @@ class StepPlan:
         self.head_coef = torch.zeros(BS, **f32)
         self.kl_coef = torch.zeros(BS, **f32)
         self.num_iter = torch.zeros(1, **f32)                             # BetaVAE-B counter (beta_vae.py:132)
+        # InfoVAE's MMD term (vae_mmd_fwd): the prior sample (an input, or drawn on the device:
+        # use_device_prior), dmmd/dz, the mmd value (vae_elbo_fwd's mmd_out) and the tile partials
+        self.prior = self.dz_mmd = self.mmd = self.mmd_ws = None
+        if self.loss_kind == L.LOSS_INFO and training:
+            self.prior = torch.zeros(B, D, **f32)
+            self.dz_mmd = torch.zeros(B, D, **f32)
+            self.mmd = torch.zeros(1, **f32)
+            self._mmd_scale = torch.zeros(1, **f32)                       # drop-in backward: dL/dloss * mmd_coef
         # backward buffers (gradients w.r.t. pre-activation of each stored tensor)
         self.g_enc = [torch.empty_like(t) for t in self.enc]
         self.g_h0 = torch.empty_like(self.h0)
@@ -573,6 +591,7 @@ class StepPlan:
             self.n_encode = len(F)
             self.n_decode0 = len(F)            # (decode() of a fused plan starts at the reparameterization)
             F.append(("vae_latent_dec_fwd", F[-1][1]))
+            self._add_mmd(F)                   # (behind the kernel that draws / reads this step's eps)
         a = L.LinearArgs(dtype=T, m=B, n=2 * D, k=4 * h[-1])
         a.x = self.enc[-1].data_ptr()
         a.x_xf = self.bn_xf(enc_pre[-1], L.X_BN_ACT, cnt(self.enc[-1]), running=True)
@@ -585,6 +604,7 @@ class StepPlan:
             self._add(F, "vae_linear_fwd", a)
             self.n_encode = len(F)             # calls of encode(): encoder + fc_mu|fc_var
             F.append(("vae_reparam_fwd", self._reparam))
+            self._add_mmd(F)
             self.n_decode0 = len(F)            # decode(): decoder_input .. head
             # ------------------------------------------------------------ decoder_input
             a = L.LinearArgs(dtype=T, m=BS, n=4 * r[0], k=D)
@@ -639,6 +659,9 @@ class StepPlan:
         e.per_img = self.per_img.data_ptr()
         e.head_coef = self.head_coef.data_ptr()
         e.kl_coef = self.kl_coef.data_ptr()
+        if self.mmd_ws is not None:
+            self._info_coefs(e, self.beta, self.alpha, self.reg_weight)
+            e.mmd_tiles, e.mmd_partials, e.mmd_out = self._mmd_tiles, self.mmd_ws.data_ptr(), self.mmd.data_ptr()
         self.n_decode1 = len(F)
         self.elbo_args = e
         # elbo_in_head: the loss evaluated by the head backward (vaehip.h vae_head_args.elbo: one
@@ -819,6 +842,35 @@ class StepPlan:
                 self.bwd_sums(a, enc_pre[i - 1])
                 self._add(Bw, "vae_conv2d_bwd_data", a)
 
+    def _info_coefs(self, e, beta: float, alpha: float, reg_weight: float) -> float:
+        """The weights of info_vae.py:145-147 in vae_elbo_args; returns the MMD coefficient."""
+        e.recon_weight, e.kl_factor = beta, 1.0 - alpha
+        e.mmd_coef = (alpha + reg_weight - 1.0) / (self.B * (self.B - 1))
+        return e.mmd_coef
+
+    def _add_mmd(self, F):
+        """InfoVAE: the MMD of this step's latents (recomputed in fp32 from mu | log_var and eps)
+        against the prior sample, right behind the reparameterization.  In a fused-loss plan the call
+        is part of the forward and adds its share of d[mu|log_var] itself (its coefficient is a
+        constant of the plan); in a drop-in plan it runs at loss_function time (run_elbo) with
+        grad_scale 1 and the backward applies the stored dz scaled by dL/dloss (seed_mmd)."""
+        if self.loss_kind != L.LOSS_INFO or not self.training:
+            return
+        B, D = self.B, self.net.latent_dim
+        a = self._mmd = L.MmdArgs(kind=MMD_KINDS[self.kernel_type], batch=B, latent=D, latent_var=self.latent_var)
+        a.mulv, a.eps, a.prior, a.dz = (self.mulv.data_ptr(), self.eps.data_ptr(), self.prior.data_ptr(),
+                                        self.dz_mmd.data_ptr())
+        nbytes, self._mmd_tiles = L.mmd_workspace(a)
+        self.mmd_ws = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.net.device)
+        a.workspace, a.workspace_bytes = self.mmd_ws.data_ptr(), nbytes
+        if self.fused_loss:
+            a.grad_scale = (self.alpha + self.reg_weight - 1.0) / (B * (B - 1))
+            a.dmulv = self.dmulv.data_ptr()
+            self._add(F, "vae_mmd_fwd", a)
+        else:
+            a.grad_scale = 1.0
+            self._keep.append(a)
+
     def _add_recon_loss(self, F):
         """The recon_loss call closing the forward (vae_recon_loss): loss terms into `out`, per-image
         MSE from the head's SSE, and dL/drecon into grad_recon for the backward."""
@@ -899,6 +951,18 @@ class StepPlan:
         self._eps_step = step                       # keep the counter alive with the plan
         return True
 
+    def use_device_prior(self, step: torch.Tensor, seed: int = 1265) -> bool:
+        """InfoVAE: draw the prior sample of compute_mmd (torch.randn_like(z), info_vae.py:220) on the
+        device inside vae_mmd_fwd, every step: the generator of use_device_eps on another stream word,
+        keyed by `seed` and the device step counter `step`; the draw is written to self.prior.  Works on
+        both bottleneck routes; returns False for a plan without an MMD term."""
+        if self.mmd_ws is None:
+            return False
+        a = self._mmd
+        a.prior_gen, a.prior_step, a.prior_seed = 1, step.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF
+        self._prior_step = step
+        return True
+
     # ------------------------------------------------------------------ execution
     def _run(self, calls, stream):
         run_calls(self, calls, stream)
@@ -931,6 +995,8 @@ class StepPlan:
                                "(elbo_in_head); run backward() first")
         o = self.out.tolist()
         third = "KLD"
+        if self.loss_kind == L.LOSS_INFO:       # info_vae.py:148
+            return {"loss": o[0], "Reconstruction_Loss": o[1], "MMD": float(self.mmd), third: o[2]}
         return {"loss": o[0], "Reconstruction_Loss": o[1], third: o[2]}
 
     # ------------------------------------------------------------------ drop-in ELBO
@@ -939,10 +1005,11 @@ class StepPlan:
     # and seeds the backward from the kernel's coefficients (seed_fused) instead of autograd's
     # dL/drecon and dL/d[mu|log_var].
     LOSS_KINDS = {"vanilla": L.LOSS_VANILLA, "betaH": L.LOSS_BETA_H, "betaB": L.LOSS_BETA_B,
-                  "iwae": L.LOSS_IWAE}
+                  "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO}
 
     def run_elbo(self, stream, loss: str, kld_weight: float, beta: float = 4.0, gamma: float = 1000.0,
-                 c_max: float = 25.0, c_stop_iter: float = 1e5, num_iter: Optional[int] = None):
+                 c_max: float = 25.0, c_stop_iter: float = 1e5, num_iter: Optional[int] = None,
+                 alpha: float = -0.5, reg_weight: float = 100.0, prior: Optional[torch.Tensor] = None):
         """vae_elbo_fwd over this step's SSE and mu|log_var: out = [loss, Reconstruction_Loss, KLD
         as the reference reports it, raw KLD]; per_img; head_coef / kl_coef = dloss/dsse_i and the
         per-row KL gradient coefficient (the backward seeds)."""
@@ -953,7 +1020,23 @@ class StepPlan:
         e.kld_weight, e.beta, e.gamma, e.c_max, e.c_stop_iter = kld_weight, beta, gamma, c_max, c_stop_iter
         if num_iter is not None:
             self.num_iter.fill_(float(num_iter))
+        if e.kind == L.LOSS_INFO:
+            # the MMD of this forward's latents into dz_mmd (unscaled) and the partials the loss adds
+            if self.mmd_ws is None or self.fused_loss:
+                raise ValueError("run_elbo('info') needs a drop-in plan built with loss='info'")
+            if prior is not None:
+                self.prior.copy_(prior.detach().reshape(self.prior.shape))
+            self.mmd_coef = self._info_coefs(e, beta, alpha, reg_weight)
+            L.call("vae_mmd_fwd", self._mmd, stream)
         L.call("vae_elbo_fwd", e, stream)
+
+    def seed_mmd(self, g_loss: torch.Tensor, mmd_coef: float, stream):
+        """Drop-in backward of the MMD term: dmulv += reparameterization backward of
+        (dL/dloss * mmd_coef) * dz_mmd (vae_mmd_reseed), next to the two seeds seed_fused switches on.
+        dmulv is zero here (the step head or reset_backward) and the backward accumulates onto it."""
+        torch.mul(g_loss.reshape(1).to(self._mmd_scale), mmd_coef, out=self._mmd_scale)
+        L.call("vae_mmd_reseed", self.B, self.net.latent_dim, self.dz_mmd.data_ptr(), self._mmd_scale.data_ptr(),
+               self.mulv.data_ptr(), self.eps.data_ptr(), self.dmulv.data_ptr(), stream)
 
     def seed_fused(self, on: bool):
         """Backward seeding of a drop-in plan: on — from head_coef / kl_coef (run_elbo); off — from
@@ -990,6 +1073,7 @@ class StepPlan:
             self.db8h.zero_()
 
 
+MMD_KINDS = {"imq": L.MMD_IMQ, "rbf": L.MMD_RBF}
 BATCH_FN = "vae_conv_bwd_filter_batch"
 DEFERRED_FNS = frozenset(("vae_conv2d_bwd_filter", "vae_convT2d_bwd_filter", "vae_unpad_accumulate"))
 

@@ -19,6 +19,7 @@ from __future__ import annotations
 import argparse
 import os
 import random
+import warnings
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -197,6 +198,10 @@ def main(argv=None) -> Dict[str, float]:
             optims, scheds = opt_cfg, []
         best, step = float("inf"), 0
         epochs = config['trainer_params'].get('max_epochs', 1)
+        if config['trainer_params'].get('gradient_clip_val') and rank == 0:
+            # (configs/vae/infovae.yaml sets it; the fused step has no clipping stage — INTEGRATION.md)
+            warnings.warn("trainer_params.gradient_clip_val is set but not applied by vae_amd.run: "
+                          "gradients are not clipped", stacklevel=1)
         graphed = None
         if args.engine == 'graph' and hasattr(model, 'fused_train_step') and len(optims) == 1 and _fusable(model):
             # the fused step replayed from HIP graphs (DDP gradient mean and rank-0 buffers inside
