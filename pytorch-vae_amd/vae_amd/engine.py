@@ -333,13 +333,19 @@ class TrainStep:
         self.opt.v.copy_(state[3]); self.opt.step.copy_(state[4]); self.plan.num_iter.copy_(state[5])
         self.net.sync_lowp()
         self.graphs = []
+        # With a process group up, its watchdog thread polls the events of the collectives issued
+        # before a capture (an event query per outstanding work, every 100 ms).  Under the default
+        # "global" capture mode a query from ANY thread is an error while a capture is open, and the
+        # watchdog ends the process on it ("operation not permitted when stream is capturing");
+        # "thread_local" keeps the capture's checks to the capturing thread.
+        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"
         if self.graph_comm:
             cs = self.comm_stream
             with torch.cuda.stream(cs):         # communicators up before the capture records them
                 dist.all_reduce(torch.zeros(1, device=self.net.device), group=self.pg)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
+            with torch.cuda.graph(g, stream=s, capture_error_mode=mode):
                 for k in range(len(self.buckets)):
                     self._segment(k)
                     _, b0, b1 = self.buckets[k]
@@ -370,7 +376,7 @@ class TrainStep:
             # launch from the host — two graphs per step left an ~8.7 us gap between them
             # (profiles/r3a: the replay of the optimizer graph behind the backward graph)
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
+            with torch.cuda.graph(g, stream=s, capture_error_mode=mode):
                 self._segment(0)
                 self._opt()
             self.graphs.append(g)
@@ -379,11 +385,11 @@ class TrainStep:
             return
         for k in range(len(self.buckets)):
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
+            with torch.cuda.graph(g, stream=s, capture_error_mode=mode):
                 self._segment(k)
             self.graphs.append(g)
         self.g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.g_opt, stream=s):
+        with torch.cuda.graph(self.g_opt, stream=s, capture_error_mode=mode):
             self._opt()
         torch.cuda.synchronize()
 

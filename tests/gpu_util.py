@@ -61,6 +61,43 @@ def tol(dtype):
     return 2e-5 if dtype == torch.float32 else 2e-2
 
 
+def vq_argmin_clear(z, E):
+    """fp64 nearest code of every row of z [rows, dim] in the codebook E [codes, dim] by the
+    reference's formula (Σz² + ΣE²) − 2 z·E (vq_vae.py:30-32), and the rows whose winner an fp32
+    evaluation of that formula cannot change.  Returns (argmin, clear mask).
+
+    A row is clear when its top-2 distance gap exceeds 2·(2·dim + 4)·2⁻²⁴·(|z|² + max_k|E_k|²):
+    Σz², ΣE² and z·E are fma chains of length dim, so each carries at most dim·u relative to its
+    sum of magnitudes (u = 2⁻²⁴, fp32 round-to-nearest), and |2 z·E| ≤ |z|² + |E_k|²; the add of
+    the two norms, the doubling and the final subtraction add at most 4u of the same scale.  One
+    distance is therefore off by at most (2·dim + 4)·u·(|z|² + |E_k|²), and two distances can
+    swap order only inside twice that."""
+    z, E = z.double(), E.double()
+    zz, ee = (z * z).sum(1), (E * E).sum(1)
+    dist = zz[:, None] + ee[None, :] - 2.0 * (z @ E.t())
+    want = torch.argmin(dist, dim=1)
+    top2 = torch.topk(dist, 2, dim=1, largest=False).values
+    bar = 2.0 * (2 * z.shape[1] + 4) * 2.0 ** -24 * (zz + ee.max())
+    return want, (top2[:, 1] - top2[:, 0]) > bar
+
+
+def check_vq_indices(latpre, E, indices, tag, slope=0.01):
+    """A VQ step's code indices against the fp64 argmin over the latents the quantizer itself read:
+    lrelu(latpre) of the step's stored pre-activation latents [..., dim] (device, the step's dtype)
+    and the fp32 codebook E [codes, dim] the step ran with.  Exact on every clear row
+    (vq_argmin_clear), and at least 95 % of the rows must be clear."""
+    pre = latpre.detach().float().cpu().reshape(-1, E.shape[1])
+    want, clear = vq_argmin_clear(torch.nn.functional.leaky_relu(pre, slope), E.detach().float().cpu())
+    idx = indices.cpu()
+    assert idx.numel() == pre.shape[0]
+    n_clear = int(clear.sum())
+    mism = int((idx[clear] != want[clear]).sum())
+    print(f"{tag}: {n_clear} of {idx.numel()} rows clear ({100.0 * n_clear / idx.numel():.2f} %), "
+          f"{mism} clear rows differ from the fp64 argmin, {int((idx != want).sum())} rows differ in total")
+    assert n_clear >= 0.95 * idx.numel(), (n_clear, idx.numel())
+    assert mism == 0, mism
+
+
 def give_workspace(a, *fns):
     """Query the workspace the calls `fns` need for args `a` (vae_*_workspace_size), allocate
     it and point `a` at it; returns the buffer (keep it alive until the calls are done)."""

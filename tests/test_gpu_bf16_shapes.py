@@ -160,6 +160,11 @@ def test_vq_b128_bf16_tracks_autocast_oracle_every_gradient():
     names = launched(lambda: step(xs))
     torch.cuda.synchronize()
     idx = plan.indices.cpu()
+    # index agreement in the timed mode: the quantizer's codes against the fp64 argmin over the
+    # step's own bf16 latents, exact on every clear row.  The codebook is the one the step's forward
+    # read, sd's — the replayed step ends in Adam, which has already moved the network's copy.
+    from gpu_util import check_vq_indices
+    check_vq_indices(plan.latpre, sd["vq_layer.embedding.weight"], plan.indices, "VQ B=128 bf16")
     o32, oac = _oracles("VQVAE", sd, x, None, M_N=0.0, vq_beta=0.25, vq_indices=idx)
     _loss_bar([plan.loss_dict()[k] for k in ("loss", "Reconstruction_Loss", "VQ_Loss")], o32, oac,
               ("loss", "Reconstruction_Loss", "VQ_Loss"))

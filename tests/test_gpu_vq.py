@@ -85,11 +85,14 @@ def test_vq_step_matches_reference():
 
 
 def test_vq_step_bf16_close():
-    """bf16 throughput mode at B=8: loss terms within 2e-2 of the teacher-forced oracle."""
+    """bf16 throughput mode at B=8: the indices equal the fp64 argmin over the step's own bf16
+    latents on every clear row; loss terms within 2e-2 of the teacher-forced oracle."""
+    from gpu_util import check_vq_indices
     from oracle import vae_oracle as O
     meta, _ = load_case("vq_b4")
     x = torch.rand(8, 3, 64, 64, generator=torch.Generator().manual_seed(7))
     sd, x, net, plan, opt = _step(meta, torch.bfloat16, x=x)
+    check_vq_indices(plan.latpre, sd["vq_layer.embedding.weight"], plan.indices, "VQ B=8 bf16")
     o = O.train_step("VQVAE", sd, x, M_N=0.0, lr=meta["lr"], vq_beta=meta["ctor"]["beta"],
                      vq_indices=plan.indices.cpu(), do_adam=False)
     got = plan.loss_dict()
@@ -141,6 +144,181 @@ def test_vq_kernel_vs_torch(rows, codes, dim):
     assert abs(float(sse) * (1 + beta) / (rows * dim) - float(vq_loss)) <= 1e-5 * float(vq_loss)
     np.testing.assert_allclose(dlat.cpu().numpy(), pre_g.numpy(), rtol=1e-5, atol=1e-9)
     np.testing.assert_allclose(dE.cpu().numpy(), Ew.grad.numpy(), rtol=1e-4, atol=1e-9)
+
+
+def _vq_call(dtype, pre, E, act, dq=None, beta=0.25, s=None, dE0=None):
+    """vae_vq_fwd (and vae_vq_bwd when dq is given) through the C ABI with VQStepPlan's operand
+    types: lat / q / dq / dlat in `dtype`, codebook / dcodebook / sse fp32, indices int64.
+    Returns the outputs on the CPU and the launch log."""
+    from gpu_util import launched
+    from vae_amd import _lib as L
+    rows, dim = pre.shape
+    codes = E.shape[0]
+    lat_d, E_d = pre.to("cuda", dtype), E.cuda()
+    idx = torch.full((rows,), -1, dtype=torch.int64, device="cuda")
+    q = torch.empty(rows, dim, device="cuda", dtype=dtype)
+    sse = torch.zeros(1, device="cuda")
+    a = L.VqArgs(dtype=L.dtype_code(dtype), rows=rows, dim=dim, codes=codes, beta=beta)
+    a.lat = lat_d.data_ptr()
+    a.lat_xf = L.Xform(kind=L.X_ACT, channels=1, slope=0.01) if act else L.Xform(kind=L.X_NONE)
+    a.codebook, a.indices, a.q, a.sse = E_d.data_ptr(), idx.data_ptr(), q.data_ptr(), sse.data_ptr()
+    st = L.stream_ptr()
+    out, keep = {}, []
+    if dq is not None:
+        dq_d = dq.to("cuda", dtype)
+        dlat = torch.empty(rows, dim, device="cuda", dtype=dtype)
+        dE = torch.zeros(codes, dim, device="cuda") if dE0 is None else dE0.clone().cuda()
+        a.dq, a.dlat, a.dcodebook = dq_d.data_ptr(), dlat.data_ptr(), dE.data_ptr()
+        if s is not None:
+            keep.append(torch.full((1,), s, device="cuda"))
+            a.loss_grad = keep[0].data_ptr()
+
+    def run():
+        L.call("vae_vq_fwd", a, st)
+        if dq is not None:
+            L.call("vae_vq_bwd", a, st)
+    out["log"] = launched(run)
+    torch.cuda.synchronize()
+    if dq is not None:
+        out.update(dlat=dlat.float().cpu(), dE=dE.cpu())
+    out.update(idx=idx.cpu(), q=q.float().cpu(), sse=float(sse))
+    return out
+
+
+# rows, codes, dim, lat_xf ACT (else NONE), loss_grad scalar (else NULL), dcodebook starts nonzero
+VQ_OP_CASES = [
+    (1000, 512, 64, True, None, False),    # the step's shape and arguments: four full 128-code chunks
+    (333, 200, 32, True, 0.37, False),     # a full chunk, then 72 codes: ragged last 16-code block
+    (257, 129, 64, False, None, True),     # second chunk of one code; 4 full workgroups + 1 row
+    (130, 1100, 16, False, 0.37, True),    # nine chunks; codes > 1024: bwd on the LM=false kernel
+    (64, 7, 16, True, None, False),        # fewer codes than one 16-lane block
+]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("rows,codes,dim,act,s,acc", VQ_OP_CASES)
+def test_vq_kernel_vs_fp64(rows, codes, dim, act, s, acc, dtype):
+    """vae_vq_fwd / vae_vq_bwd in fp32 and in bf16 (vq_fwd_kernel<__bf16, D, 1>, vq_bwd_kernel<__bf16, LM>)
+    against the reference's formulas (vq_vae.py:24-55) in fp64, evaluated on the values the kernel
+    reads (the bf16-rounded latents and dq in bf16 mode).
+
+    Branches reached (csrc/vae_vq.hip): a partial last LDS chunk after a full one (codes 200, 129,
+    1100); a last 16-code block with idle lanes (200, 129, 1100, 7); the last workgroup with one row
+    (257); vq_bwd_kernel<T, false>, direct global atomics (codes 1100 > 1024); lat_xf NONE (two
+    cases) and ACT; loss_grad != NULL (two cases, s = 0.37: it scales the commitment and embedding
+    terms, not dq, so the reference loss is s·vq_loss + (st_q·dq).sum()); dcodebook accumulated
+    onto a nonzero start (two cases, one per bwd kernel).
+
+    Indices are exact on every clear row (gpu_util.vq_argmin_clear: gap above twice the worst-case
+    fp32 rounding of the distance formula), and at least 95 % of the rows must be clear — measured
+    on the CPU for these seeds: 100 % in every case but 257 x 129 x 64 in bf16 (one row short, 99.6 %)."""
+    from gpu_util import vq_argmin_clear
+    beta = 0.25
+    g = torch.Generator().manual_seed(rows + codes)
+    pre = torch.randn(rows, dim, generator=g).to(dtype).float()
+    E = (torch.rand(codes, dim, generator=g) * 2 - 1) * 0.5
+    dq = (torch.randn(rows, dim, generator=g) * 1e-3).to(dtype).float()
+    # the nonzero start has the gradient's own scale 2 / (rows·dim), so that the fp32 rounding of
+    # start + increment (2⁻²⁴ of it) stays far below the increment's 1e-9 absolute bar
+    dE0 = torch.randn(codes, dim, generator=g) * (2.0 / (rows * dim)) if acc else torch.zeros(codes, dim)
+    out = _vq_call(dtype, pre, E, act, dq=dq, beta=beta, s=s, dE0=dE0)
+    got = out["idx"]
+    # the instantiations this case is here for, <element type, dim, 1> and <element type, LM>, by
+    # their mangled names (f = float, DF16b = __bf16, which not every demangler knows)
+    ty = "f" if dtype == torch.float32 else "DF16b"
+    assert f"vq_fwd_kernelI{ty}Li{dim}ELi1EE" in out["log"], out["log"]
+    assert f"vq_bwd_kernelI{ty}Lb{int(codes <= 1024)}EE" in out["log"], out["log"]
+    # the kernel's own fp32 activation of the stored latent, then everything in fp64
+    slope = float(torch.tensor(0.01, dtype=torch.float32))
+    z = (torch.nn.functional.leaky_relu(pre, 0.01) if act else pre).double().requires_grad_(True)
+    Ew = E.double().requires_grad_(True)
+    want, clear = vq_argmin_clear(z.detach(), E)
+    share = float(clear.double().mean())
+    assert int(got.min()) >= 0 and int(got.max()) < codes, (int(got.min()), int(got.max()))
+    mism = int((got[clear] != want[clear]).sum())
+    assert share >= 0.95, share
+    assert mism == 0, mism
+    qq = Ew[got]
+    mse = torch.nn.functional.mse_loss
+    vq_loss = mse(qq.detach(), z) * beta + mse(qq, z.detach())
+    st_q = z + (qq - z).detach()
+    sv = 1.0 if s is None else float(torch.tensor(s, dtype=torch.float32))
+    (sv * vq_loss + (st_q * dq.double()).sum()).backward()
+    pre_g = z.grad * torch.where(pre > 0, 1.0, slope).double() if act else z.grad
+    assert torch.equal(out["q"], E[got].to(dtype).float())
+    e_sse = abs(out["sse"] * (1 + beta) / (rows * dim) - float(vq_loss)) / float(vq_loss)
+    d_lat = (out["dlat"].double() - pre_g).abs()
+    inc = out["dE"].double() - dE0.double()
+    d_E = (inc - Ew.grad).abs()
+    print(f"vq {rows}x{codes}x{dim} {'bf16' if dtype == torch.bfloat16 else 'fp32'}: clear {100 * share:.2f} %, "
+          f"sse rel {e_sse:.2e}, dlat max rel {float((d_lat / pre_g.abs().clamp_min(1e-6)).max()):.2e}, "
+          f"dcodebook max err / max {float(d_E.max() / Ew.grad.abs().max()):.2e}")
+    assert e_sse <= 1e-5, e_sse
+    if dtype == torch.float32:
+        np.testing.assert_allclose(out["dlat"].numpy(), pre_g.numpy(), rtol=1e-5, atol=1e-9)
+    else:
+        # one bf16 rounding of an fp32 value.  bf16 keeps 8 significant bits, so round-to-nearest is
+        # off by at most 2⁻⁸ / (1 + 2⁻⁸) of the value (reached just above a power of two: 3.89e-3
+        # measured in every case); the fp32 value's own error, 2e-6 here, fits in the 1.5e-5 left
+        assert bool((d_lat <= 2.0 ** -8 * pre_g.abs() + 1e-9).all()), float((d_lat - 2.0 ** -8 * pre_g.abs()).max())
+    np.testing.assert_allclose(inc.numpy(), Ew.grad.numpy(), rtol=1e-4, atol=1e-9)
+    unpicked = torch.bincount(got, minlength=codes) == 0
+    assert torch.equal(out["dE"][unpicked], dE0[unpicked])      # codes no row picked: untouched, bit for bit
+
+
+# duplicate code -> the base code it copies bit for bit
+VQ_TIE_DUPS = {1: 0, 21: 5, 140: 9, 33: 2, 290: 2}
+
+
+def _vq_tie_case(dtype):
+    """(pre, E, planted rows, their expected index) of the forced-tie test: codes 300, dim 64,
+    rows 128 (two workgroups), bf16-representable codebook values so that a latent can equal a
+    code bit for bit in both dtypes."""
+    g = torch.Generator().manual_seed(300)
+    E = ((torch.rand(300, 64, generator=g) * 2 - 1) * 0.5).bfloat16().float()
+    for dup, base in VQ_TIE_DUPS.items():
+        E[dup] = E[base]
+    pre = torch.randn(128, 64, generator=g).to(dtype).float()
+    # every third row: rows 0, 3, ..., 126 sit at 43 different positions of the 64-row tile (all
+    # four waves, all four accumulator rows of a lane), cycling through the four base codes
+    planted = torch.arange(0, 128, 3)
+    expect = torch.tensor([0, 5, 9, 2])[(planted // 3) % 4]
+    pre[planted] = E[expect]
+    return pre, E, planted, expect
+
+
+def _check_vq_ties(got, planted, expect):
+    """The planted rows got the smallest index of their tied set; a duplicate ties bit for bit
+    with its base code on EVERY row, so under first-minimum it wins nowhere."""
+    assert torch.equal(got[planted], expect), (got[planted].tolist(), expect.tolist())
+    dups = torch.tensor(sorted(VQ_TIE_DUPS))
+    assert not bool(torch.isin(got, dups).any()), got[torch.isin(got, dups)].tolist()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_vq_first_minimum_on_forced_ties(dtype):
+    """torch.argmin's first-minimum tie-break at each level of vq_fwd_kernel, forced: a third of the
+    rows EQUAL a code that has exact duplicates, so the duplicates share the minimum distance bit
+    for bit (same data, same fma order) and only the tie-break decides.
+      E[1] = E[0]      neighbouring lane of the same 16-code block: the (distance, index) shuffle combine
+      E[21] = E[5]     same lane (code % 16), next block: strict < in the lane's ascending scan
+      E[140] = E[9]    next 128-code LDS chunk, another lane: lane 9's best, carried in registers
+                       over the two later chunks, against lane 12's equal one in the combine
+      E[33] = E[290] = E[2]   290 in lane 2 two chunks later (strict < against the carried best) and
+                       33 in lane 1 (combine): two levels at once
+    codes 300 also ends in a partial chunk (44 codes); lat_xf NONE.  A stand-in that breaks ties
+    toward the LAST index fails _check_vq_ties on every planted row (checked on the CPU)."""
+    from gpu_util import vq_argmin_clear
+    pre, E, planted, expect = _vq_tie_case(dtype)
+    out = _vq_call(dtype, pre, E, act=False)
+    got = out["idx"]
+    assert int(got.min()) >= 0 and int(got.max()) < 300
+    _check_vq_ties(got, planted, expect)
+    assert torch.equal(out["q"][planted], E[expect])            # bf16-representable: exact in both dtypes
+    # the random rows: exact wherever the fp64 argmin is clear (a row nearest to a duplicated code
+    # has gap 0 and is not)
+    want, clear = vq_argmin_clear(pre, E)
+    assert torch.equal(got[clear], want[clear])
 
 
 @pytest.mark.parametrize("dtype,ld", [(torch.float32, 0), (torch.bfloat16, 0), (torch.float32, 8), (torch.bfloat16, 8)])
