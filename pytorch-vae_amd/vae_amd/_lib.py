@@ -359,7 +359,7 @@ class FilterBatch:
         self.kinds = (c_int32 * n)(*[self.FNS[fn] for fn, _ in self.calls])
         self.items = (c_void_p * n)(*[ctypes.addressof(ref._obj) for _, ref in self.calls])
         self.workspace, self.workspace_bytes = None, 0
-        self.side = False            # run on the plan's side stream (net.run_calls)
+        self.side = False            # run on the plan's side stream (calls.run_calls)
         # scalar-argument calls that read this batch's output (vae_unpad_accumulate of a padded
         # gradient): run right behind it on the same stream, whichever stream that is
         self.after = []

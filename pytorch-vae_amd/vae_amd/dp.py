@@ -20,6 +20,9 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from . import _lib as L
+from .calls import structs
+
 # fields of the argument structs that point into the gradient buffer
 _GRAD_FIELDS = ("dw", "db", "dcodebook", "dw1", "db1", "dw2", "db2")
 _XF_GRAD_FIELDS = ("dgamma_out", "dbeta_out")
@@ -53,15 +56,10 @@ def last_writers(calls: Sequence, grads: torch.Tensor, layout):
     starts = [p.offset for p in params]
     last = [-1] * len(params)
     for i, (fn, ref) in enumerate(calls):
-        if ref is None:
-            continue
-        if hasattr(ref, "args"):                # a batch of weight-gradient calls (net.FilterBatch)
-            ptrs = [p for a in ref.args for p in _written_grad_ptrs(a)]
-            ptrs += [r[4] for f, r in getattr(ref, "after", []) if f == "vae_unpad_accumulate"]
-        elif isinstance(ref, tuple):            # scalar-argument entry points
-            ptrs = [ref[4]] if fn == "vae_unpad_accumulate" else []
-        else:
-            ptrs = _written_grad_ptrs(ref._obj if hasattr(ref, "_obj") else ref)
+        ptrs = [p for a in structs(ref) for p in _written_grad_ptrs(a)]
+        # the scalar-argument calls that write gradients: this one, or those riding behind a batch
+        scalar = ref.after if isinstance(ref, L.FilterBatch) else [(fn, ref)]
+        ptrs += [r[4] for f, r in scalar if f == "vae_unpad_accumulate"]
         for ptr in ptrs:
             off = (ptr - base) // 4
             if not 0 <= off < layout.total:

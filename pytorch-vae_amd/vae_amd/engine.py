@@ -16,15 +16,16 @@ import torch
 import torch.distributed as dist
 
 from . import _lib as L
+from .calls import BATCH_FN, call_one
 from .dp import BucketedAllReduce, broadcast_buffers, final_prefix, plan_buckets
-from .net import BATCH_FN, VAENet, call_one
+from .plan import DEFERRED_MSG, NetBase
 
 
 class FusedAdam:
     """torch.optim.Adam semantics (lerp first moment, bias-corrected) over the flat buffer;
     also refreshes the bf16 weight copy in the same pass.  step and lr are device scalars."""
 
-    def __init__(self, net: VAENet, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+    def __init__(self, net: NetBase, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None):
         self.net = net
         # m / v may be given: a torch.optim.Adam's exp_avg / exp_avg_sq of the same flat
@@ -73,7 +74,7 @@ class FusedAdam:
                self.v.data_ptr(), self.step.data_ptr(), self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
                self.weight_decay, net.lowp.data_ptr() if net.lowp is not None else None,
                stream if stream is not None else L.stream_ptr())
-        if getattr(net, "swap_descs", None) is not None:
+        if net.swap_descs:
             if refresh_swaps:
                 net.refresh_swaps(stream)
             else:
@@ -103,8 +104,8 @@ def begin_args(plan, step: torch.Tensor):
     a.npad = npad
     # the swapped-axes weight copies the bf16 GEMMs read (net.swap_descs), refreshed in the same
     # launch from the weights the previous step's optimizer wrote
-    sw = getattr(plan.net, "swap_descs", None)
-    if isinstance(sw, ctypes.Array) and 0 < len(sw) <= L.SWAP_MAX:      # (VQNet: several arrays)
+    if plan.net.swaps_in_step_begin and plan.net.swap_descs:            # (VQNet: its own launches)
+        sw, = plan.net.swap_descs
         a.nswap = len(sw)
         for i in range(len(sw)):
             a.swap[i] = sw[i]
@@ -128,27 +129,31 @@ class TrainStep:
                  overlap: bool = True, comm_dtype: torch.dtype = torch.float32, split_adam: bool = True,
                  device_prior: Optional[int] = None):
         self.net, self.plan, self.opt = net, plan, opt
+        self.zero_eps = False       # models.Autoencoder: eps stays zero (z = mu), never drawn
         # device_eps = seed: the forward draws eps itself every step (StepPlan.use_device_eps, keyed
         # by the optimizer's step counter) — the reference's per-step randn_like inside the step
-        self.device_eps = (device_eps is not None and hasattr(plan, "use_device_eps")
-                           and plan.use_device_eps(opt.step, device_eps))
+        self.device_eps = device_eps is not None and plan.use_device_eps(opt.step, device_eps)
         # device_prior = seed (InfoVAE): the MMD kernel draws its prior sample itself every step
         # (StepPlan.use_device_prior; info_vae.py:220's randn_like), keyed by the same step counter
-        self.device_prior = (device_prior is not None and hasattr(plan, "use_device_prior")
-                             and plan.use_device_prior(opt.step, device_prior))
+        self.device_prior = device_prior is not None and plan.use_device_prior(opt.step, device_prior)
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.use_graph = graph
-        self.segments = []                      # (call range) of the backward per bucket
         # force_buckets: the bucketed path (segment graphs, one all-reduce per bucket, the buffer
         # broadcast) at world size 1 too — how the one-GPU tests run the RCCL branch
-        if self.world > 1 or (force_buckets and self.world == 1 and dist.is_available() and dist.is_initialized()):
-            raw = getattr(plan, "bwd_calls_raw", plan.bwd_calls)
-            self.buckets = plan_buckets(raw, plan.grads, net.layout, nbuckets)
-            if hasattr(plan, "batch_wgrads"):
-                # the weight gradients of each bucket's segment as one batch at its end
-                ends = plan.batch_wgrads([b[0] for b in self.buckets])
-                self.buckets = [(e, s, t) for e, (_, s, t) in zip(ends, self.buckets)]
+        exchange = self.world > 1 or (force_buckets and dist.is_available() and dist.is_initialized())
+        # one rank: the backward's weight-gradient slab reductions (and the loss fused into the head
+        # backward) run inside the optimizer launch (StepPlan.defer_reductions, vae_adam_step_ex);
+        # with more ranks the gradients must be complete before their all-reduce — which a plan that
+        # another step has deferred cannot give any more
+        will_defer = defer_reductions and not exchange
+        if plan.deferred and not will_defer:
+            raise RuntimeError(DEFERRED_MSG)
+        if exchange:
+            self.buckets = plan_buckets(plan.bwd_calls_raw, plan.grads, net.layout, nbuckets)
+            # the weight gradients of each bucket's segment as one batch at its end (a plan that batches)
+            ends = plan.batch_wgrads([b[0] for b in self.buckets])
+            self.buckets = [(e, s, t) for e, (_, s, t) in zip(ends, self.buckets)]
             # the last bucket also carries the loss terms (plan.metrics sits right after the
             # gradients): their rank mean is the reference's log_dict(sync_dist=True) at no extra
             # collective (experiment.py:55)
@@ -207,20 +212,15 @@ class TrainStep:
         # begin_ex=False keeps vae_step_begin + the padding calls (tests/test_gpu_routes.py)
         self._begin = begin_args(plan, opt.step) if begin_ex else None
         self._begin_swaps = self._begin is not None and self._begin[0].nswap > 0
-        # one rank: the backward's weight-gradient slab reductions (and the loss fused into the head
-        # backward) run inside the optimizer launch (StepPlan.defer_reductions, vae_adam_step_ex);
-        # with more ranks the gradients must be complete before their all-reduce
-        self.deferred = (self.comm is None and defer_reductions and hasattr(plan, "defer_reductions")
-                         and plan.defer_reductions())
+        self.deferred = will_defer and plan.defer_reductions()
         self._slabs, self._elbo = [], None
         # one rank, the decoder's weight gradients on the plan's side stream (StepPlan(wg_overlap=True)):
         # the optimizer splits at the gradients final once that batch has run (their prefix of the
         # buffer, ordered by backward completion) — Adam over the prefix runs on the side stream right
         # behind the batch, beside the encoder's backward; Adam over the rest on the main stream
         self._adam_split = 0
-        if self.deferred and split_adam and getattr(plan, "wg_overlap", False) and getattr(plan, "side", None) is not None:
-            si = next((i for i, (fn, ref) in enumerate(plan.bwd_calls)
-                       if fn == BATCH_FN and getattr(ref, "side", False)), None)
+        if self.deferred and split_adam and plan.wg_overlap and plan.side is not None:
+            si = next((i for i, (fn, ref) in enumerate(plan.bwd_calls) if fn == BATCH_FN and ref.side), None)
             if si is not None:
                 t = final_prefix(plan.bwd_calls, si, plan.grads, net.layout)
                 if 0 < t < plan.grads.numel() and t % 4 == 0:
@@ -243,7 +243,7 @@ class TrainStep:
             if p.loss_kind == L.LOSS_BETA_B:
                 p.num_iter.add_(1.0)
             p._run(p.fwd_calls[skip:], st)
-            if self.comm is not None and not getattr(p, "elbo_in_head", False):
+            if self.comm is not None and not p.elbo_in_head:
                 p.metrics.copy_(p.out)
                 if p.loss_kind == L.LOSS_INFO:
                     # the fourth logged term of an InfoVAE step (each rank's MMD is over its own
@@ -267,7 +267,7 @@ class TrainStep:
             # (the same pointers at every run: each deferring call has a workspace of its own)
             self._slabs, self._elbo = L.deferred_take()
             self._keep_written(p)
-        if k == 0 and self.comm is not None and getattr(p, "elbo_in_head", False):
+        if k == 0 and self.comm is not None and p.elbo_in_head:
             # the loss terms come from the head backward (vae_head_args.elbo), the first call of
             # segment 0's backward: copied behind it, reduced with the last bucket as before
             p.metrics.copy_(p.out)
@@ -306,7 +306,7 @@ class TrainStep:
         elif self.deferred:
             self.opt.apply_deferred(self.plan.grads, self._slabs, self._elbo, L.stream_ptr())
         if self.deferred:
-            if getattr(self.net, "swap_descs", None) is not None:
+            if self.net.swap_descs:
                 if self._begin_swaps:
                     self.net.swaps_stale = True
                 else:
@@ -315,11 +315,12 @@ class TrainStep:
         self.opt.apply(self.plan.grads, L.stream_ptr(), refresh_swaps=not self._begin_swaps)
 
     def _capture(self):
-        # warm up on a side stream (allocations, lazy init), then capture
+        # warm up on a side stream (allocations, lazy init), then capture.  The state the warm-up step
+        # changes is saved first: the side stream waits for these copies (its first launch bumps opt.step)
         s = self.stream
-        s.wait_stream(torch.cuda.current_stream())
         state = (self.net.params.clone(), self.net.running.clone(), self.opt.m.clone(), self.opt.v.clone(),
                  self.opt.step.clone(), self.plan.num_iter.clone())
+        s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for k in range(len(self.buckets)):
                 self._segment(k)

@@ -260,10 +260,10 @@ class GraphedSteps:
             step = self.steps[B] = model.fused_train_step(B, opt=self.fused, **self.kw)
             # eps drawn inside the step on the device (Philox keyed by a seed from torch's generator,
             # so manual_seed still fixes the run) where the fused bottleneck can; else plan.eps below
-            if hasattr(step.plan, "use_device_eps") and not getattr(step, "zero_eps", False):
+            if not step.zero_eps:
                 step.device_eps = step.plan.use_device_eps(self.fused.step, int(torch.randint(0, 2 ** 62, (1,))))
             # InfoVAE: the prior sample of its MMD term drawn the same way, inside vae_mmd_fwd
-            if getattr(step.plan, "prior", None) is not None:
+            if step.plan.prior is not None:
                 step.device_prior = step.plan.use_device_prior(self.fused.step, int(torch.randint(0, 2 ** 62, (1,))))
         lr = self.opt.param_groups[0]['lr']
         if lr != self._lr:                            # (a device scalar: written only on change)
@@ -272,10 +272,8 @@ class GraphedSteps:
         self._img_shape = tuple(imgs.shape[1:])
         exp.curr_device = imgs.device
         plan = step.plan
-        if hasattr(plan, "eps") and not getattr(step, "zero_eps", False) and not getattr(step, "device_eps", False):
-            plan.eps.normal_()                        # torch.randn_like(std), vanilla_vae.py:116
-        if getattr(plan, "prior", None) is not None and not getattr(step, "device_prior", False):
-            plan.prior.normal_()                      # torch.randn_like(z), info_vae.py:220
+        # the step's random inputs the device does not draw itself (the reference's randn_like calls)
+        plan.draw_noise(eps=not (step.zero_eps or step.device_eps), prior=not step.device_prior)
         step(imgs)
         self.nstep += 1
         self.opt.state[model.flat]['step'] = torch.tensor(float(self.nstep))
@@ -297,14 +295,12 @@ class GraphedSteps:
         dev = imgs.device
         if self._ext is None:
             ie = plan.x[0].numel()
-            third = "VQ_Loss" if not hasattr(plan, "eps") else "KLD"
-            info = getattr(plan, "prior", None) is not None                     # InfoVAE: a fourth term
+            info = plan.prior is not None                                       # InfoVAE: a fourth term
             self._terms_buf = torch.zeros(4 if info else 3, device=dev)
-            self._terms = {'loss': self._terms_buf[0], 'Reconstruction_Loss': self._terms_buf[1],
-                           third: self._terms_buf[2]}
+            self._terms = {k: self._terms_buf[i] for i, k in enumerate(plan.loss_names)}
             if info:
                 self._terms['MMD'] = self._terms_buf[3]
-            if getattr(step, "zero_eps", False):                                # Autoencoder
+            if step.zero_eps:                                                   # Autoencoder
                 z = torch.zeros((), device=dev)
                 self._terms.update(KLD=z, feature_loss=z)
             self._ext = {'best': torch.tensor([float('-inf'), float('inf')], device=dev),

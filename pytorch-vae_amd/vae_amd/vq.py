@@ -23,13 +23,15 @@ from typing import Dict, List, Optional
 import torch
 
 from . import _lib as L
-from .layout import Layout, default_init, vq_layout, vq_param_spec
-from .net import MAT_MIN_FLOPS, SLOPE, _pad4, make_swaps, run_calls, size_workspaces
+from .calls import structs
+from .layout import vq_layout, vq_param_spec
+from .net import MAT_MIN_FLOPS, SLOPE
+from .plan import NetBase, PlanBase, ZeroRegion, make_swaps
 
 NRES = 6             # ResidualLayers per stack (vq_vae.py:111, :138)
 
 
-class VQNet:
+class VQNet(NetBase):
     """Parameters of the VQVAE on one device (flat fp32 master + bf16 GEMM copy)."""
 
     def __init__(self, in_channels: int = 3, embedding_dim: int = 64, num_embeddings: int = 512,
@@ -44,29 +46,11 @@ class VQNet:
         self.img_size = img_size
         if img_size % (2 ** len(self.hidden_dims)):
             raise ValueError("img_size must be divisible by 2**len(hidden_dims)")
-        self.dtype = dtype
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.layout: Layout = vq_layout(in_channels, embedding_dim, num_embeddings, self.hidden_dims)
-        self.ref_order = [n for n, _, _ in vq_param_spec(in_channels, embedding_dim, num_embeddings, self.hidden_dims)]
-        cpu_p = torch.zeros(self.layout.total)
-        default_init(self.layout, cpu_p, torch.zeros(0), generator)
-        self.params = cpu_p.to(self.device)
-        self.running = torch.zeros(1, dtype=torch.float32, device=self.device)   # no BatchNorm
-        self.lowp = (torch.zeros(self.layout.total, dtype=torch.bfloat16, device=self.device)
-                     if dtype == torch.bfloat16 else None)
-        self.num_batches_tracked = 0
-        self.wt_t: Dict[str, int] = {}
-        self.swap_descs = None
+        spec = vq_param_spec(in_channels, embedding_dim, num_embeddings, self.hidden_dims)
+        super().__init__(vq_layout(in_channels, embedding_dim, num_embeddings, self.hidden_dims),
+                         [n for n, _, _ in spec], dtype, device, generator)
+        self.lowp_t: List[torch.Tensor] = []        # the swapped copies, one buffer per descriptor array
         self.sync_lowp()
-
-    @property
-    def dcode(self) -> int:
-        return L.dtype_code(self.dtype)
-
-    def sync_lowp(self):
-        if self.lowp is not None:
-            L.call("vae_cast_bf16", self.params.numel(), self.params.data_ptr(), self.lowp.data_ptr(), L.stream_ptr())
-            self.refresh_swaps()
 
     def ensure_swaps(self, names):
         """bf16 mode: swapped-axes copies (vaehip.h wt_t) of the named weights — the ones the bf16
@@ -79,17 +63,11 @@ class VQNet:
         if not new:
             return
         # copies already handed out stay where they are (plans built earlier point at them)
-        chunks, bufs = list(self.swap_descs or ()), list(getattr(self, "lowp_t", ()))
         for i in range(0, len(new), L.SWAP_MAX):
             d, b = make_swaps(self.layout, self.params, new[i:i + L.SWAP_MAX], self.device, self.wt_t)
-            chunks.append(d)
-            bufs.append(b)
-        self.swap_descs, self.lowp_t = chunks, bufs
+            self.swap_descs.append(d)
+            self.lowp_t.append(b)
         self.refresh_swaps()
-
-    def refresh_swaps(self, stream=None):
-        for d in self.swap_descs or ():
-            L.call("vae_swap_axes", len(d), ctypes.byref(d), stream if stream is not None else L.stream_ptr())
 
     def name_of_lowp(self, ptr: int) -> Optional[str]:
         """Parameter name whose bf16 copy starts at device pointer `ptr` (None: not a bf16 weight)."""
@@ -101,23 +79,6 @@ class VQNet:
                 return s.name
         return None
 
-    def load_reference_state_dict(self, sd: Dict[str, torch.Tensor]):
-        self.layout.load_reference(self.params, self.running, {k: v.to(self.device) for k, v in sd.items()})
-        self.sync_lowp()
-
-    def reference_state_dict(self) -> Dict[str, torch.Tensor]:
-        return self.layout.export_reference(self.params, None, 0, self.ref_order)
-
-    def p(self, name: str) -> int:
-        s = self.layout.by_name[name]
-        return self.params.data_ptr() + 4 * s.offset
-
-    def w(self, name: str) -> int:
-        s = self.layout.by_name[name]
-        if self.lowp is not None:
-            return self.lowp.data_ptr() + 2 * s.offset
-        return self.params.data_ptr() + 4 * s.offset
-
 
 def _act(slope: float = SLOPE, aux: Optional[torch.Tensor] = None) -> L.Xform:
     xf = L.Xform(kind=L.X_ACT, channels=1, slope=slope)
@@ -126,7 +87,7 @@ def _act(slope: float = SLOPE, aux: Optional[torch.Tensor] = None) -> L.Xform:
     return xf
 
 
-class VQStepPlan:
+class VQStepPlan(PlanBase):
     """Buffers and prebuilt launches of one VQ-VAE training step for a fixed batch.
 
     grads land in `self.grads` (net.params layout); `zero` (grads, per-image SSE, the VQ SSE)
@@ -134,17 +95,18 @@ class VQStepPlan:
     from `grad_recon` (dL/drecon) and `vq_grad` (dL/dvq_loss) instead of the fixed loss."""
 
     loss_kind = L.LOSS_VQ
+    loss_names = ("loss", "Reconstruction_Loss", "VQ_Loss")
 
     def __init__(self, net: VQNet, batch: int, *, beta: float = 0.25, fused_loss: bool = True, concurrent: bool = False,
                  materialise: bool = True, mat_min_flops: float = MAT_MIN_FLOPS):
         # materialise=False: the large strided layers keep their LeakyReLU fused into the GEMM's
         # operand load instead of one vae_bn_apply pass (tests/test_gpu_routes.py)
-        self.net, self.B, self.beta, self.fused_loss = net, batch, beta, fused_loss
+        super().__init__(net)
+        self.B, self.beta, self.fused_loss = batch, beta, fused_loss
         self.materialise, self.mat_min_flops = bool(materialise), float(mat_min_flops)
         dev, T = net.device, net.dtype
         h, E, img = net.hidden_dims, net.embedding_dim, net.img_size
         B = batch
-        self._keep = []
         f32 = dict(dtype=torch.float32, device=dev)
         act = dict(dtype=T, device=dev)
         self.x = torch.zeros(B, 3, img, img, **f32)
@@ -154,7 +116,6 @@ class VQStepPlan:
             sp //= 2
             self.enc.append(torch.empty(B, sp, sp, c, **act))
         self.s, C = sp, h[-1]
-        self.lat_hw = sp
         m = (B, sp, sp, C)
         self.e_in = torch.empty(*m, **act)                          # encoder Conv3x3 output
         self.e_t = [torch.empty(*m, **act) for _ in range(NRES)]    # residual Conv3x3 outputs
@@ -175,11 +136,10 @@ class VQStepPlan:
         # GEMM operand stays on the packed path (vae_pad_channels / vae_unpad_accumulate)
         self.pad_rgb = T == torch.bfloat16
         self.cy = 8 if self.pad_rgb else 3
-        r_ = h[::-1]
         if self.pad_rgb:
             self.x8 = torch.zeros(B, img, img, 8, **act)
             self.w8e = torch.zeros(h[0] * 16 * 8, **act)            # encoder.0 [Co][4][4][8]
-            self.w8d = torch.zeros(r_[-1] * 16 * 8, **act)          # output ConvT [Ci][4][4][8]
+            self.w8d = torch.zeros(r[-1] * 16 * 8, **act)          # output ConvT [Ci][4][4][8]
             self.b8d = torch.zeros(8, **f32)
         self.y = torch.empty(B, img, img, self.cy, **act)           # pre-Tanh output
         self.recon = torch.empty(B, 3, img, img, **f32)
@@ -198,21 +158,19 @@ class VQStepPlan:
         self.g_q = torch.empty_like(self.q)
         self.g_lat = torch.empty_like(self.latpre)
         self.g_enc = [torch.empty_like(t) for t in self.enc]
-        nz = _pad4(net.layout.total) + 4 + _pad4(B) + 4
-        self.zero = torch.zeros(nz, **f32)
-        o = 0
-        self.grads = self.zero[o:o + net.layout.total]; o += _pad4(net.layout.total)
-        self.metrics = self.zero[o:o + 4]; o += 4                  # rank-averaged loss terms (engine.py)
-        self.sse = self.zero[o:o + B]; o += _pad4(B)
-        self.vq_sse = self.zero[o:o + 1]; o += 4
+        zr = ZeroRegion()
+        zr.add("grads", net.layout.total)
+        zr.add("metrics", 4)                                        # rank-averaged loss terms (engine.py)
+        zr.add("sse", B)
+        zr.add("vq_sse", 1)
+        z = zr.alloc(dev)
+        self.zero, self.grads, self.metrics, self.sse, self.vq_sse = (z[k] for k in ("zero", "grads", "metrics", "sse", "vq_sse"))
         self.step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.fwd_calls: List = []
-        self.bwd_calls: List = []
         self._mat: Dict[int, torch.Tensor] = {}     # materialised lrelu(t) of large layers' inputs (by t)
         self.side = torch.cuda.Stream(device=dev) if concurrent else None     # weight gradients (run_calls)
         self._build()
         self._attach_swaps()
-        size_workspaces(self, [self.fwd_calls, self.bwd_calls])
+        self.size_workspaces()
 
     def _attach_swaps(self):
         """Point every data gradient and transposed-conv forward at the net's swapped-axes weight
@@ -223,23 +181,16 @@ class VQStepPlan:
             return
         use = []
         for fn, ref in self.fwd_calls + self.bwd_calls:
-            if fn in ("vae_conv2d_bwd_data", "vae_convT2d_fwd") and not isinstance(ref, tuple):
-                name = net.name_of_lowp(ref._obj.wt or 0)
-                if name is not None:
-                    use.append((ref._obj, name))
+            if fn in ("vae_conv2d_bwd_data", "vae_convT2d_fwd"):
+                for a in structs(ref):
+                    name = net.name_of_lowp(a.wt or 0)
+                    if name is not None:
+                        use.append((a, name))
         net.ensure_swaps([n for _, n in use])
         for arg, name in use:
             arg.wt_t = net.wt_t[name]
 
     # ------------------------------------------------------------------ helpers
-    def g(self, name: str) -> int:
-        s = self.net.layout.by_name[name]
-        return self.grads.data_ptr() + 4 * s.offset
-
-    def _add(self, lst, fn, arg):
-        self._keep.append(arg)
-        lst.append((fn, ctypes.byref(arg)))
-
     def _conv(self, t_in, cin, cout, r, stride, pad, transposed=False):
         n, hh, ww = t_in.shape[0], t_in.shape[1], t_in.shape[2]
         if transposed:
@@ -328,6 +279,10 @@ class VQStepPlan:
         r = h[::-1]
         iup = 1 + NRES + 1
         wout = f"decoder.{iup + len(r) - 1}.0"                      # output ConvT (-> 3 channels)
+
+        def strided(i, cin):        # encoder.i: Conv(k4, s2, p1) on the (img >> i)-wide map
+            return L.ConvArgs(dtype=T, n=B, h=img >> i, w=img >> i, c=cin, k=h[i], p=img >> (i + 1), q=img >> (i + 1),
+                              r=4, stride=2, pad=1)
         if self.pad_rgb:
             F.append(("vae_nchw_to_nhwc_pad", (T, B, 3, img, img, 8, self.x.data_ptr(), self.x8.data_ptr())))
             F.append(("vae_pad_channels", (T, h[0] * 16, 3, 8, net.w("encoder.0.0.weight"), self.w8e.data_ptr())))
@@ -337,10 +292,8 @@ class VQStepPlan:
         for i in range(nh):
             src = self.x if i == 0 else self.enc[i - 1]
             cin = 3 if i == 0 else h[i - 1]
-            a = L.ConvArgs(dtype=net.dcode, n=B, h=src.shape[2], w=src.shape[3] if i == 0 else src.shape[2], c=cin,
-                           k=h[i], p=self.enc[i].shape[1], q=self.enc[i].shape[2], r=4, stride=2, pad=1)
+            a = strided(i, cin)
             if i == 0:
-                a.h = a.w = img
                 if self.pad_rgb:
                     a.c, a.x = 8, self.x8.data_ptr()
                 else:
@@ -482,10 +435,7 @@ class VQStepPlan:
         self._add(Bw, "vae_conv2d_bwd_filter", f)
         for i in reversed(range(nh)):
             cin = 3 if i == 0 else h[i - 1]
-            hin = img if i == 0 else self.enc[i - 1].shape[1]
-            mk = lambda: L.ConvArgs(dtype=net.dcode, n=B, h=hin, w=hin, c=cin, k=h[i], p=self.enc[i].shape[1],
-                                    q=self.enc[i].shape[2], r=4, stride=2, pad=1)
-            f = mk()
+            f = strided(i, cin)
             if i == 0 and self.pad_rgb:
                 f.c, f.x = 8, self.x8.data_ptr()
             elif i == 0:
@@ -499,25 +449,7 @@ class VQStepPlan:
                 f.dw_inner = 3          # dW straight into [128][4][4][3] from the 8-channel image
             self._add(Bw, "vae_conv2d_bwd_filter", f)
             if i > 0:
-                a = mk()
+                a = strided(i, cin)
                 a.dy, a.wt = self.g_enc[i].data_ptr(), net.w(f"encoder.{i}.0.weight")
                 a.dx, a.dx_epi = self.g_enc[i - 1].data_ptr(), _act(SLOPE, self.enc[i - 1])
                 self._add(Bw, "vae_conv2d_bwd_data", a)
-
-    # ------------------------------------------------------------------ execution
-    def _run(self, calls, stream):
-        run_calls(self, calls, stream)
-
-    def begin(self, stream=None):
-        stream = stream if stream is not None else L.stream_ptr()
-        L.call("vae_step_begin", self.zero.data_ptr(), self.zero.numel() * 4, self.step.data_ptr(), stream)
-
-    def forward(self, stream=None):
-        self._run(self.fwd_calls, stream if stream is not None else L.stream_ptr())
-
-    def backward(self, stream=None):
-        self._run(self.bwd_calls, stream if stream is not None else L.stream_ptr())
-
-    def loss_dict(self) -> Dict[str, float]:
-        o = self.out.tolist()
-        return {"loss": o[0], "Reconstruction_Loss": o[1], "VQ_Loss": o[2]}

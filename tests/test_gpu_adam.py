@@ -24,7 +24,7 @@ def test_fused_adam_matches_torch_adam(wd, lr, betas):
     ref = p0.clone().requires_grad_(True)
     opt = torch.optim.Adam([ref], lr=lr, betas=betas, eps=1e-8, weight_decay=wd)
     net = types.SimpleNamespace(params=p0.cuda(), lowp=torch.zeros(n, dtype=torch.bfloat16, device="cuda"),
-                                device=torch.device("cuda"))
+                                device=torch.device("cuda"), swap_descs=[])     # (plan.NetBase: no swapped copies)
     fa = FusedAdam(net, lr=lr, betas=betas, eps=1e-8, weight_decay=wd)
     st = L.stream_ptr()
     for k, gk in enumerate(grads):

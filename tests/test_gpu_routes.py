@@ -137,3 +137,21 @@ def test_vq_route(opts):
               ("loss", "Reconstruction_Loss", "VQ_Loss"))
     g16 = {k: v.cpu() for k, v in net.layout.export_reference(plan.grads).items()}
     assert _grad_bar(g16, o32, oac, f"VQ route {opts}") == len(o32["grads"])
+
+
+def test_deferred_plan_refuses_a_bare_backward_and_a_non_deferring_step():
+    """a one-rank TrainStep leaves its plan's weight-gradient reductions to the optimizer
+    launch (StepPlan.defer_reductions), for good.  What would then read unreduced partial gradients
+    without any error — plan.backward() on its own, a second step that does not defer — raises
+    instead.  Construction only: nothing is launched beyond the nets' own setup."""
+    from vae_amd.engine import FusedAdam, TrainStep
+    from vae_amd.net import StepPlan, VAENet
+    net = VAENet(latent_dim=128, dtype=torch.bfloat16, device="cuda")
+    plan = StepPlan(net, 4)
+    opt = FusedAdam(net, lr=0.005)
+    step = TrainStep(net, plan, opt, graph=False)
+    assert step.deferred
+    with pytest.raises(RuntimeError, match="TrainStep.*defer_reductions=False"):
+        plan.backward()
+    with pytest.raises(RuntimeError, match="TrainStep.*defer_reductions=False"):
+        TrainStep(net, plan, opt, defer_reductions=False)

@@ -13,7 +13,7 @@ def main():
     arch = sys.argv[1] if len(sys.argv) > 1 else "vq"
     B = int(sys.argv[2]) if len(sys.argv) > 2 else 4
     from vae_amd import _lib as L
-    from vae_amd.net import call_one
+    from vae_amd.calls import call_one, structs
     torch.cuda.set_device(0)
     if arch == "vq":
         from vae_amd.vq import VQNet, VQStepPlan
@@ -26,13 +26,12 @@ def main():
     plan.x.copy_(torch.rand(plan.x.shape, device="cuda"))
     torch.cuda.synchronize()
     st = L.stream_ptr()
-    print("swaps", len(getattr(net, "swap_descs", None) or []), flush=True)
+    print("swaps", sum(len(d) for d in net.swap_descs), flush=True)
     for i, (fn, ref) in enumerate(plan.fwd_calls + plan.bwd_calls):
-        a = getattr(ref, "_obj", None)
         desc = ""
-        if a is not None and hasattr(a, "r") and hasattr(a, "stride"):
-            desc = f"n={a.n} h={a.h} c={a.c} k={a.k} r={a.r} s={a.stride} wt_t={bool(a.wt_t)} ws={a.workspace_bytes}"
-        print(f"{i:3d} {fn} {desc}", flush=True)
+        for a in (a for a in structs(ref) if isinstance(a, L.ConvArgs)):
+            desc += f" n={a.n} h={a.h} c={a.c} k={a.k} r={a.r} s={a.stride} wt_t={bool(a.wt_t)} ws={a.workspace_bytes}"
+        print(f"{i:3d} {fn}{desc}", flush=True)
         call_one(fn, ref, st)
         torch.cuda.synchronize()
     print("ok", flush=True)

@@ -30,7 +30,8 @@ def main():
     args = ap.parse_args()
     from vae_amd import _lib as L
     from vae_amd.engine import FusedAdam, TrainStep
-    from vae_amd.net import StepPlan, VAENet, call_one
+    from vae_amd.calls import call_one, structs
+    from vae_amd.net import StepPlan, VAENet
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     net = VAENet(latent_dim=128, dtype=dtype, device="cuda", generator=torch.Generator().manual_seed(0))
     plan = StepPlan(net, args.batch)
@@ -49,17 +50,17 @@ def main():
     for i in only:
         fn, ref = calls[i]
         for s in splits:
-            obj = getattr(ref, "_obj", None)
-            if obj is not None and hasattr(obj, "split_k"):
-                obj.split_k = s
-            elif s != 0:
+            objs = [a for a in structs(ref) if hasattr(a, "split_k")]
+            for a in objs:
+                a.split_k = s
+            if not objs and s != 0:
                 continue
             torch.cuda._sleep(1000)                      # marker kernel (spin_kernel)
             for _ in range(args.reps):
                 call_one(fn, ref, sp)
             groups.append({"launch": i, "fn": fn, "split": s})
-            if obj is not None and hasattr(obj, "split_k"):
-                obj.split_k = 0
+            for a in objs:
+                a.split_k = 0
     torch.cuda._sleep(1000)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)

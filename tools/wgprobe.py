@@ -30,7 +30,8 @@ def main():
     args = ap.parse_args()
     from vae_amd import _lib as L
     from vae_amd.engine import FusedAdam, TrainStep
-    from vae_amd.net import StepPlan, VAENet, call_one
+    from vae_amd.calls import call_one, structs
+    from vae_amd.net import StepPlan, VAENet
     lib = L.load()
     assert "probe" in lib._name, "load the probe build (VAE_HIP_LIB=probe)"
     net = VAENet(latent_dim=128, dtype=torch.bfloat16, device="cuda", generator=torch.Generator().manual_seed(0))
@@ -51,7 +52,7 @@ def main():
     torch.cuda.synchronize()
     sp = L.stream_ptr()
     idx = [i for i, (fn, _) in enumerate(plan.bwd_calls) if fn == "vae_conv_bwd_filter_batch"]
-    items = [(fn, ref._obj) for fn, ref in plan.bwd_calls_raw if fn in ("vae_conv2d_bwd_filter", "vae_convT2d_bwd_filter")]
+    items = [(fn, structs(ref)[0]) for fn, ref in plan.bwd_calls_raw if fn in ("vae_conv2d_bwd_filter", "vae_convT2d_bwd_filter")]
     for k, (fn, a) in enumerate(items):
         print(f"item {k}: {fn} n={a.n} {a.h}x{a.w}x{a.c} -> {a.p}x{a.q}x{a.k}")
     out = []
