@@ -7,7 +7,8 @@ weight gradients and Adam), every buffer the step wrote is still on the device. 
 recomputed on the CPU in fp64 from the GPU's OWN inputs to that op (teacher forcing: the stored
 bf16 activations and gradients, the bf16 weight copy Adam read, the fp32 master parameters), with
 the kernels' operand rounding mirrored (a transformed operand, lrelu(BN(y)) or the BatchNorm-
-backward a*g + b*y + c, is rounded to bf16 before the product, as the kernels stage it), and
+backward a*g + b*y + c, is rounded to bf16 before the product, as the kernels stage it; the fc
+weight gradients' activation operand by the kernel's own fp32 arithmetic, BN.act_f32), and
 compared with the GPU's output of that op:
 
   * bf16 outputs (activations, data gradients): elementwise |got - ref| <= 2^-7 |ref| + 2e-3 rms(ref)
@@ -89,6 +90,36 @@ class BN:
     def act(self):
         """The consumer's operand: bf16(lrelu(BN(y)))."""
         return bf(lrelu(self.z))
+
+    def act_f32(self, sums, shift):
+        """The same operand by the bottleneck kernels' own fp32 arithmetic (csrc/vae_latent.hip
+        bn_coef and its callers: the replicas' sums added in order, s1 = Σ/M, var = fma(Σ², 1/M, -s1²),
+        a = γ/sqrt(var + eps), b = fma(-mean, a, β), bf16(lrelu(fma(y, a, b)))), every step rounded
+        to fp32.  `sums`: the producer's fp32 [2][reps][C]; `shift`, γ, β: the fp32 master values.
+
+        act() forms z in fp64 from the same statistics; the two differ by ~1e-6 of z (the fp32
+        cancellation in var and b), which moves a value across a bf16 rounding boundary in ~0.2 % of
+        the elements.  A sum over B rows dilutes such a flip; at B = 1 the fc weight gradient is the
+        outer product of ONE activation row, so a flip is the whole error of its column (up to 2^-8 of
+        max|dW|, over the 2e-3 bar) and the reference needs the operand the kernel really formed.
+        (BetaVAE-H at B = 1: the operand read back from the rank-1 gradient, dW[j][k] / g[j], differs
+        from act() in 1 of 2048 elements, 2.3e-3 of max|dW|, and from this one in none.)"""
+        f = lambda t: t.to(torch.float32)
+        fma = lambda a, b, c: (a.double() * b.double() + c.double()).to(torch.float32)   # one rounding
+        ts, tq = f(sums[0][0]), f(sums[1][0])
+        for r in range(1, sums.shape[1]):
+            ts, tq = ts + f(sums[0][r]), tq + f(sums[1][r])
+        inv_m = torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(self.M), dtype=torch.float32)
+        s1 = ts * inv_m
+        var = fma(tq, inv_m, -(s1 * s1))
+        var = torch.clamp(var, min=0.0)
+        mean = s1 + f(shift)
+        invstd = torch.tensor(1.0, dtype=torch.float32) / torch.sqrt(var + torch.tensor(BN_EPS, dtype=torch.float32))
+        a = f(self.gamma) * invstd
+        b = fma(-mean, a, f(self.beta))
+        v = lambda t: t.view(1, -1, 1, 1)
+        z = fma(f(self.y), v(a).expand_as(self.y), v(b).expand_as(self.y))
+        return bf(torch.where(z > 0, z, z * torch.tensor(SLOPE, dtype=torch.float32)))
 
     def ambiguous(self):
         return self.z.abs() < 1e-5 * self.z.abs().max()
@@ -322,10 +353,13 @@ class StepCheck:
         self.add("d mu|logvar", ("vae_latent_dec_bwd", 0), cmp_f32(cpu64(p.dmulv).view(B, -1), dmulv))
         gd = cpu64(p.dmulv).view(B, -1)
         g16 = bf(gd)                     # (the bottleneck kernels stage d[mu|logvar] as a bf16 operand)
+        # (the activation operand as the kernel's own fp32 arithmetic rounds it: BN.act_f32)
+        last = f"encoder.{len(h) - 1}"
+        act4k = bns[-1].act_f32(p.bnfwd[last + ".1"].detach().cpu(), self.P[last + ".0.bias"]).flatten(1)
         self.add("fc_mu.weight grad", ("vae_latent_fc_bwd", 0),
-                 cmp_f32(self.G["fc_mu.weight"], g16[:, :gd.shape[1] // 2].t() @ act4))
+                 cmp_f32(self.G["fc_mu.weight"], g16[:, :gd.shape[1] // 2].t() @ act4k))
         self.add("fc_var.weight grad", ("vae_latent_fc_bwd", 0),
-                 cmp_f32(self.G["fc_var.weight"], g16[:, gd.shape[1] // 2:].t() @ act4))
+                 cmp_f32(self.G["fc_var.weight"], g16[:, gd.shape[1] // 2:].t() @ act4k))
         self.add("fc_mu|fc_var bias grad", ("vae_latent_fc_bwd", 0),
                  cmp_f32(torch.cat([self.G["fc_mu.bias"], self.G["fc_var.bias"]]), gd.sum(0)))
         wcat = torch.cat([self.W["fc_mu.weight"], self.W["fc_var.weight"]], 0)

@@ -90,6 +90,48 @@ def test_bgemm_convT2d_bwd_data(shape):
     assert "bgemm_kernel" in log, log
 
 
+# ---------------------------------------------------------------------------------------------
+# A partial last batch on the big_ae deep layers.  N = 29 is the smallest odd batch whose deep
+# layers still pass the kernels' 4 GFLOP floor (bgemm_ok / bwg_ok), so M = N*p*q ends inside a
+# 128-row tile and the weight gradients' pixel count inside a 64-pixel K-step.
+
+FWD_LAST = [
+    (29, 512, 1024, 8, 2, 3, 1),        # M = 464 = 3*128 + 80
+    (29, 1024, 2048, 4, 2, 3, 1),       # M = 116 < one tile; deep split-K + finalize
+]
+
+
+@pytest.mark.parametrize("shape", FWD_LAST)
+def test_bgemm_conv2d_fwd_last_batch(shape):
+    from vae_amd import _lib as L
+    log = _launched(lambda: run_fwd(False, *shape, L.X_NONE))
+    print(log)
+    assert "bgemm_kernel" in log, log
+
+
+def test_bgemm_convT2d_fwd_last_batch():
+    from vae_amd import _lib as L
+    log = _launched(lambda: run_fwd(True, 29, 2048, 1024, 2, 2, 3, 1, L.X_NONE))       # M = 116 per phase
+    print(log)
+    assert "bgemm_kernel" in log, log
+
+
+@pytest.mark.parametrize("epi", ["bn_act", "act"])
+def test_bgemm_conv2d_bwd_data_last_batch(epi):
+    from vae_amd import _lib as L
+    e = L.X_BN_ACT if epi == "bn_act" else L.X_ACT
+    log = _launched(lambda: run_dgrad(False, 29, 512, 1024, 8, 2, 3, 1, L.X_NONE, e))
+    print(log)
+    assert "bgemm_kernel" in log, log
+
+
+def test_bgemm_convT2d_bwd_data_last_batch():
+    from vae_amd import _lib as L
+    log = _launched(lambda: run_dgrad(True, 29, 1024, 512, 4, 2, 3, 1, L.X_NONE, L.X_BN_ACT))
+    print(log)
+    assert "bgemm_kernel" in log, log
+
+
 def test_bn_apply_matches_torch():
     """vae_bn_apply: lrelu(BN(y)) from a coefficient table, lrelu(y), and A g + B y + C."""
     from gpu_util import nhwc
@@ -141,4 +183,26 @@ def test_bwg_weight_gradient(shape):
     from vae_amd import _lib as L
     tr, *rest = shape
     log = _launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
+    assert "bwg_kernel" in log, log
+
+
+WGRAD_B_LAST = [  # pixel counts that are no multiple of the 64-pixel K-step
+    (False, 29, 1024, 2048, 4, 2, 3, 1),    # 116 output pixels = 64 + 52
+    (True, 29, 2048, 1024, 2, 2, 3, 1),     # 116 input pixels
+    (True, 29, 1024, 512, 4, 2, 3, 1),      # 464 = 7 * 64 + 16, one K slice
+    # several K slices with the ragged step in the last one: bwg_launch gives 72 tiles 3 slices of
+    # 9 K-steps (576 pixels); 107 * 16 = 1712 pixels = 576 + 576 + 560, and 560 = 8 * 64 + 48.
+    # (An 8x8 or larger map has a multiple of 64 pixels at every batch, and a 4x4 map needs >= 16
+    # K-steps to be split and 4 GFLOP to reach this kernel: N = 107 is the odd batch that does.)
+    (True, 107, 512, 256, 4, 2, 3, 1),
+]
+
+
+@pytest.mark.parametrize("shape", WGRAD_B_LAST)
+def test_bwg_weight_gradient_last_batch(shape):
+    from test_gpu_cgemm import run_wgrad
+    from vae_amd import _lib as L
+    tr, *rest = shape
+    log = _launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
+    print(log)
     assert "bwg_kernel" in log, log

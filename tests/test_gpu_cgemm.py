@@ -116,9 +116,13 @@ def run_fwd(transposed, N, cin, cout, hw, stride, R, pad, kind, split=0, give_wt
     ws = give_workspace(a, "vae_convT2d_fwd" if transposed else "vae_conv2d_fwd")
     L.call("vae_convT2d_fwd" if transposed else "vae_conv2d_fwd", ctypes.byref(a), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    assert relmax(nchw(out), ref) < OUT_TOL
-    assert relmax(sums[:cout].cpu(), acc.sum((0, 2, 3))) < 1e-3
-    assert relmax(sums[cout:].cpu(), (acc * acc).sum((0, 2, 3))) < 1e-3
+    e_out, e_s1 = relmax(nchw(out), ref), relmax(sums[:cout].cpu(), acc.sum((0, 2, 3)))
+    e_s2 = relmax(sums[cout:].cpu(), (acc * acc).sum((0, 2, 3)))
+    print(f"fwd {'convT' if transposed else 'conv'} N={N} {cin}->{cout} hw={hw} R={R} kind={kind}: "
+          f"out {e_out:.2e} (bar {OUT_TOL}), sum {e_s1:.2e}, sumsq {e_s2:.2e} (bar 1e-3)")
+    assert e_out < OUT_TOL
+    assert e_s1 < 1e-3
+    assert e_s2 < 1e-3
 
 
 FWD = [  # N, cin, cout, hw, stride, R, pad
@@ -218,10 +222,16 @@ def run_dgrad(transposed, N, cin, cout, hw, stride, R, pad, dy_kind, epi_kind, g
     L.call("vae_convT2d_bwd_data" if transposed else "vae_conv2d_bwd_data", ctypes.byref(a),
            torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    assert relmax(nchw(dx), gout) < OUT_TOL
+    e_dx = relmax(nchw(dx), gout)
+    msg = f"dgrad {'convT' if transposed else 'conv'} N={N} {cin}->{cout} hw={hw} R={R}: dx {e_dx:.2e} (bar {OUT_TOL})"
     if epi_kind == L.X_BN_ACT:
-        assert relmax(dbet.cpu(), s1) < 1e-3
-        assert relmax(dgam.cpu(), s2) < 1e-3
+        e_s1, e_s2 = relmax(dbet.cpu(), s1), relmax(dgam.cpu(), s2)
+        msg += f", sum g {e_s1:.2e}, sum g*xhat {e_s2:.2e} (bar 1e-3)"
+    print(msg)
+    assert e_dx < OUT_TOL
+    if epi_kind == L.X_BN_ACT:
+        assert e_s1 < 1e-3
+        assert e_s2 < 1e-3
 
 
 DGRAD = [  # N, cin, cout, hw (input of the conv), stride, R, pad
@@ -244,6 +254,57 @@ def test_cgemm_conv2d_bwd_data(shape, give_wt_t):
 def test_cgemm_conv2d_bwd_data_plain(epi):
     L = _L()
     run_dgrad(False, 8, 256, 256, 16, 1, 3, 1, L.X_NONE, L.X_NONE if epi == "none" else L.X_ACT)
+
+
+# ---------------------------------------------------------------------------------------------
+# The partial last batch of an epoch (the data path never drops it): N = 1, 7, 19 on the deep
+# layers' 2x2 / 4x4 maps gives M = 4N / 16N rows that end inside a row tile (28 < 32; 76 = 64 + 12
+# = 2*32 + 12; 16) — the masked rows of the forward statistics and of the E_BNBWD epilogue sums.
+# Same references and bars as above; each case also asserts cgemm_kernel from the launch log.
+
+def _ran(kernel, fn):
+    from gpu_util import launched
+    log = launched(fn)
+    assert kernel in log, log
+
+
+FWD_LAST = [(7, 256, 512, 4, 2, 3, 1), (19, 256, 512, 4, 2, 3, 1)]
+CONVT_LAST = [(7, 512, 256, 2, 2, 3, 1), (19, 256, 128, 4, 2, 3, 1)]
+
+
+@pytest.mark.parametrize("shape", FWD_LAST)
+@pytest.mark.parametrize("kind", ["none", "act", "bn_act"])
+def test_cgemm_conv2d_fwd_last_batch(shape, kind):
+    L = _L()
+    k = {"none": L.X_NONE, "act": L.X_ACT, "bn_act": L.X_BN_ACT}[kind]
+    _ran("cgemm_kernel", lambda: run_fwd(False, *shape, k))
+
+
+@pytest.mark.parametrize("shape", CONVT_LAST)
+@pytest.mark.parametrize("give_wt_t", [False, True])
+def test_cgemm_convT2d_fwd_last_batch(shape, give_wt_t):
+    L = _L()
+    _ran("cgemm_kernel", lambda: run_fwd(True, *shape, L.X_BN_ACT, give_wt_t=give_wt_t))
+
+
+DGRAD_LAST = [(7, 256, 512, 4, 2, 3, 1),         # M = 112
+              (1, 256, 512, 4, 2, 3, 1),         # M = 16
+              (19, 128, 256, 8, 2, 3, 1)]
+DGRAD_T_LAST = [(7, 512, 256, 2, 2, 3, 1),       # M = 28
+                (19, 64, 32, 16, 2, 3, 1)]
+
+
+@pytest.mark.parametrize("shape", DGRAD_LAST)
+@pytest.mark.parametrize("give_wt_t", [False, True])
+def test_cgemm_conv2d_bwd_data_last_batch(shape, give_wt_t):
+    L = _L()
+    _ran("cgemm_kernel", lambda: run_dgrad(False, *shape, L.X_BN_DY, L.X_BN_ACT, give_wt_t=give_wt_t))
+
+
+@pytest.mark.parametrize("shape", DGRAD_T_LAST)
+def test_cgemm_convT2d_bwd_data_last_batch(shape):
+    L = _L()
+    _ran("cgemm_kernel", lambda: run_dgrad(True, *shape, L.X_BN_DY, L.X_BN_ACT))
 
 
 DGRAD_T = [  # N, cin, cout, hw (input of the transposed conv), stride, R, pad
@@ -300,14 +361,18 @@ class BN:
             x.aux = aux_dev.data_ptr()
         return x
 
-    def act(self):
+    def act(self, rnd=bf):
         z = F.batch_norm(self.y.double(), None, None, self.gamma.double(), self.beta.double(), True, 0.1, 1e-5)
-        return bf(F.leaky_relu(z, SLOPE).float())
+        return rnd(F.leaky_relu(z, SLOPE).float())
 
 
-def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3):
-    """One bf16 weight-gradient call's arguments (kernel-side operands) and its fp64 reference."""
+def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, fp32=False):
+    """One bf16 weight-gradient call's arguments (kernel-side operands) and its fp64 reference.
+    fp32: the parity mode's call instead (fp32 operands, nothing rounded to bf16, every partial sum
+    added in a fixed order: vae_conv_args.deterministic), against the same fp64 reference."""
     L = _L()
+    bf = (lambda t: t.float()) if fp32 else globals()["bf"]
+    nhwc = (lambda t: t.permute(0, 2, 3, 1).contiguous().to("cuda", torch.float32)) if fp32 else globals()["nhwc"]
     g = torch.Generator().manual_seed(seed)
     if transposed:
         P = (hw - 1) * stride - 2 * pad + R + (stride - 1 if R == 3 else 0)
@@ -322,7 +387,7 @@ def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, se
     bny = BN(yst, g, shift=torch.randn(cout, generator=g) * 0.1)
     # operands as the kernel forms them
     if x_kind == L.X_BN_ACT:
-        act = bnx.act()
+        act = bnx.act(bf)
     elif x_kind == L.X_ACT:
         act = bf(F.leaky_relu(xst, SLOPE))
     else:
@@ -350,7 +415,8 @@ def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, se
     dw = torch.zeros(want.shape, device="cuda")
     db = torch.zeros(cout, device="cuda")
     dgo = torch.zeros(cout, device="cuda"); dbo = torch.zeros(cout, device="cuda")
-    a = L.ConvArgs(dtype=L.BF16, n=N, h=hw, w=hw, c=cin, k=cout, p=P, q=P, r=R, stride=stride, pad=pad)
+    a = L.ConvArgs(dtype=L.F32 if fp32 else L.BF16, n=N, h=hw, w=hw, c=cin, k=cout, p=P, q=P, r=R, stride=stride,
+                   pad=pad, deterministic=1 if fp32 else 0)
     a.x = xd.data_ptr(); a.x_xf = bnx.xf(L, x_kind) if x_kind == L.X_BN_ACT else L.Xform(kind=x_kind, channels=cin, slope=SLOPE)
     a.dy = gd.data_ptr()
     if dy_kind == L.X_BN_DY:
@@ -366,7 +432,9 @@ def check_wgrad(w):
     """The call's dW (and closed-form bias / BN affine gradients) against the fp64 reference."""
     torch.cuda.synchronize()
     dw, want, R = w["dw"], w["want"], w["R"]
-    assert relmax(dw.cpu(), want) < 2e-3
+    e_dw = relmax(dw.cpu(), want)
+    print(f"{w['fn']} dW {tuple(want.shape)}: {e_dw:.2e} (bar 2e-3)")
+    assert e_dw < 2e-3
     if w["untransformed"]:
         # untransformed operands are exact bf16 in the fp64 reference: only fp32 accumulation order
         # separates the two, so the whole tensor must agree to ~1e-6 (a dropped or doubled K slice,
@@ -378,9 +446,12 @@ def check_wgrad(w):
             raise AssertionError(f"weight gradient rel-norm error {err:.3e}; per tap {per_tap}")
     if w["db_exact"] is not None:
         # closed form A*Σg + B*Σy + C*M (vaehip.h bn_args): exact up to fp32 cancellation
-        assert float((w["db"].cpu().double() - w["db_exact"]).abs().max()) < \
-            1e-6 * float(w["dyp"].double().abs().sum((0, 2, 3)).max())
-        assert relmax(w["dgo"].cpu(), w["dgam"]) < 1e-5 and relmax(w["dbo"].cpu(), w["dbet"]) < 1e-5
+        e_db = float((w["db"].cpu().double() - w["db_exact"]).abs().max())
+        b_db = 1e-6 * float(w["dyp"].double().abs().sum((0, 2, 3)).max())
+        e_dg, e_dbt = relmax(w["dgo"].cpu(), w["dgam"]), relmax(w["dbo"].cpu(), w["dbet"])
+        print(f"    bias grad {e_db:.2e} (bar {b_db:.2e}), dgamma {e_dg:.2e}, dbeta {e_dbt:.2e} (bar 1e-5)")
+        assert e_db < b_db
+        assert e_dg < 1e-5 and e_dbt < 1e-5
 
 
 def run_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3):
@@ -431,6 +502,36 @@ def test_wgemm_convT2d_vq_shape():
     run_wgrad(True, 4, 256, 128, 16, 2, 4, 1, L.X_ACT, L.X_NONE)
 
 
+# The pixel (K) tail of the weight gradients at a partial last batch: 4N = 28 pixels (less than one
+# 32-pixel K-step) and 76 = 2*32 + 12 on the output side of the conv, on the input side of the
+# transposed conv; 16N = 112 and 304 on the other operand.
+@pytest.mark.parametrize("N", [7, 19])
+def test_wgemm_conv2d_bn_last_batch(N):
+    L = _L()
+    _ran("wgemm", lambda: run_wgrad(False, N, 256, 512, 4, 2, 3, 1, L.X_BN_ACT, L.X_BN_DY))
+
+
+@pytest.mark.parametrize("N", [7, 19])
+def test_wgemm_convT2d_bn_last_batch(N):
+    L = _L()
+    _ran("wgemm", lambda: run_wgrad(True, N, 512, 256, 2, 2, 3, 1, L.X_BN_ACT, L.X_BN_DY))
+
+
+# The all-taps kernel (32 x 32 tiles, layers with fewer than 64 channels on one side) has a pixel
+# tail of its own.  In the shipped models those layers are the full-resolution ones, whose pixel
+# count is a multiple of 256 at every batch, so only a thin layer on a small map reaches it (a
+# hidden_dims list may put one there): 4N = 28 and 76 pixels.
+THIN = [(False, 32, 32, 4, 2, 3, 1), (True, 32, 32, 2, 2, 3, 1)]
+
+
+@pytest.mark.parametrize("N", [7, 19])
+@pytest.mark.parametrize("shape", THIN)
+def test_wgemm_taps_pixel_tail(shape, N):
+    L = _L()
+    tr, *rest = shape
+    _ran("wgemm_taps_kernel", lambda: run_wgrad(tr, N, *rest, L.X_BN_ACT, L.X_BN_DY))
+
+
 def test_cgemm_fwd_table_built_in_kernel():
     """Forward conv with BN_ACT from the raw statistics (no table): tab_build + running stats."""
     L = _L()
@@ -463,14 +564,12 @@ BATCH = [(True, 16, 64, 32, 16, 2, 3, 1), (True, 16, 128, 64, 8, 2, 3, 1), (True
          (False, 16, 64, 128, 16, 2, 3, 1), (False, 16, 32, 64, 32, 2, 3, 1), (False, 16, 8, 32, 64, 2, 3, 1)]
 
 
-def test_wgrad_batch_matches_reference_and_is_deterministic():
-    """vae_conv_bwd_filter_batch (one XCD-partitioned grid, K-slice partials in slabs reduced in slice
-    order): every layer's dW / bias / BN affine gradients against fp64, and two runs bit-identical."""
+def run_wgrad_batch(N, fp32=False, layers=None):
     L = _L()
     ws = []
-    for seed, (tr, N, cin, cout, hw, s_, R, pad) in enumerate(BATCH):
+    for seed, (tr, _, cin, cout, hw, s_, R, pad) in enumerate(layers or BATCH):
         xk = L.X_BN_ACT if (tr and cin != 512) or (not tr and cin != 8) else L.X_NONE
-        ws.append(prep_wgrad(tr, N, cin, cout, hw, s_, R, pad, xk, L.X_BN_DY, seed=10 + seed))
+        ws.append(prep_wgrad(tr, N, cin, cout, hw, s_, R, pad, xk, L.X_BN_DY, seed=10 + seed, fp32=fp32))
     n = len(ws)
     kinds = (ctypes.c_int32 * n)(*[L.LAYER_CONVT2D if w["fn"].startswith("vae_convT") else L.LAYER_CONV2D for w in ws])
     items = (ctypes.c_void_p * n)(*[ctypes.addressof(w["a"]) for w in ws])
@@ -491,3 +590,33 @@ def test_wgrad_batch_matches_reference_and_is_deterministic():
                 check_wgrad(w)
     for a, b in zip(*results):
         assert torch.equal(a, b)
+
+
+def test_wgrad_batch_matches_reference_and_is_deterministic():
+    """vae_conv_bwd_filter_batch (one XCD-partitioned grid, K-slice partials in slabs reduced in slice
+    order): every layer's dW / bias / BN affine gradients against fp64, and two runs bit-identical."""
+    run_wgrad_batch(16)
+
+
+@pytest.mark.parametrize("N", [7, 19])
+@pytest.mark.parametrize("mode", ["bf16", "fp32"])
+def test_wgrad_batch_last_batch(N, mode):
+    """The same nine layers at a partial last batch: the deep layers have 4N = 28 / 76 pixels, less
+    than one 64-pixel K-step of the grouped kernel (wg3_kernel) / one step and a 12-pixel tail, and
+    every layer's last K slice is ragged.  bf16: the grouped launch; fp32: the parity mode's calls
+    with their partial sums added in a fixed order.  Reference, bars and the bit-identical rerun as above."""
+    from gpu_util import launched
+    log = launched(lambda: run_wgrad_batch(N, fp32=mode == "fp32"))
+    if mode == "bf16":
+        assert "wg3_kernel" in log and "wg3_reduce" in log, log
+    else:       # the fp32 items run one by one on the VALU GEMM, K-split partials summed by its finalize
+        assert "igemm_kernel<float" in log and "igemm_finalize<float" in log and "wg3_kernel" not in log, log
+
+
+@pytest.mark.parametrize("N", [7, 19])
+def test_wgrad_batch_thin_layers_pixel_tail(N):
+    """The grouped launch's all-taps body (THIN above) with 28 / 76 pixels, beside one per-tap layer."""
+    from gpu_util import launched
+    layers = [(tr, N, *rest) for tr, *rest in THIN] + [(False, N, 256, 512, 4, 2, 3, 1)]
+    log = launched(lambda: run_wgrad_batch(N, layers=layers))
+    assert "wg3_kernel" in log, log

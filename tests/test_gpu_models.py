@@ -334,11 +334,10 @@ def test_autoencoder_against_reference(case):
                                    atol=1e-3 * meta["lr"] + 1e-7, err_msg=name)
 
 
-@pytest.mark.gpu
-def test_graph_engine_mixed_batch_sizes_share_one_adam_state():
+def _mixed_batch_sizes_share_one_adam_state(sizes):
     """every batch size's TrainStep shares ONE FusedAdam whose moments are the torch
     optimizer's own exp_avg / exp_avg_sq (the partial last batch of an epoch must not start from
-    a fresh Adam state).  Four graph steps at B = 16, 8, 16, 8; after each, that step's gradient
+    a fresh Adam state).  Four graph steps at B = `sizes` (16, 8, 16, 8); after each, that step's gradient
     (its plan's grads buffer) drives a torch.optim.Adam on a copy of the parameters (teacher
     forced): parameters and both moments must follow torch's single-state Adam to fp32 rounding.
     (A fresh state on the B = 8 steps would restart bias correction: a ~lr*sign(g) step.)"""
@@ -347,7 +346,7 @@ def test_graph_engine_mixed_batch_sizes_share_one_adam_state():
     kw = dict(in_channels=3, latent_dim=128, dtype=torch.float32, device="cuda", seed=1265)
     params = {'LR': 0.005, 'weight_decay': 0.0, 'kld_weight': 2.5e-4}
     gen = torch.Generator(device="cuda").manual_seed(5)
-    xs = [torch.rand(b, 3, 64, 64, device="cuda", generator=gen) for b in (16, 8, 16, 8)]
+    xs = [torch.rand(b, 3, 64, 64, device="cuda", generator=gen) for b in sizes]
     batches = [(x, torch.zeros(x.shape[0]), [f"{i}.png" for i in range(x.shape[0])]) for x in xs]
     model = vae_models["VanillaVAE"](**kw)
     model.train()
@@ -373,6 +372,18 @@ def test_graph_engine_mixed_batch_sizes_share_one_adam_state():
     torch.testing.assert_close(st['exp_avg_sq'], rs['exp_avg_sq'], rtol=1e-5, atol=1e-12)
     torch.testing.assert_close(model.flat.detach(), ref.detach(), rtol=1e-5, atol=1e-6)
     gs.flush()
+
+
+@pytest.mark.gpu
+def test_graph_engine_mixed_batch_sizes_share_one_adam_state():
+    _mixed_batch_sizes_share_one_adam_state((16, 8, 16, 8))
+
+
+@pytest.mark.gpu
+def test_graph_engine_ragged_last_batch_shares_one_adam_state():
+    """The same with an odd last batch, as an epoch on a dataset that is no multiple of the batch
+    ends: B = 16, 7, 16, 7 (4B = 28 rows and pixels in the deep layers)."""
+    _mixed_batch_sizes_share_one_adam_state((16, 7, 16, 7))
 
 
 @pytest.mark.parametrize("normalize,size", [(True, 64), (False, 64), (True, 40)])

@@ -7,6 +7,8 @@ launches it.
   VanillaVAE B=64        configs[1] (the headline; models/vanilla_vae.py:25-146)
   BetaVAE-H B=32         configs[2] per GPU (global 256 over 8; beta_vae.py:129-152)
   IWAE K=5 B=64          configs[3] (decoder and head at B*S = 320; iwae.py:95-160)
+  B = 1, 7, 13 (x5), 19  the partial last batch of an epoch, which the data path keeps: every GEMM
+                         dimension derived from the batch ends inside a tile or a K-step
 
 The per-kernel map is written to gpurun_out/kernel_coverage_<arch>_<B>.json (tools/kernel_coverage.py
 joins it with the profiles' kernel lists)."""
@@ -20,7 +22,11 @@ pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [("vanilla", 64, 1, True), ("betaH", 32, 1, True), ("iwae", 64, 1, True),
-         ("betaH", 32, 2, False), ("vanilla", 16, 1, True), ("vanilla", 16, 1, False)]
+         ("betaH", 32, 2, False), ("vanilla", 16, 1, True), ("vanilla", 16, 1, False),
+         # the partial last batch of an epoch (GraphedSteps builds a TrainStep for it): 4B = 28 rows and
+         # pixels (less than a 32-row tile / a 32-pixel K-step), 76 = 64 + 12, one image, 13 x 5 = 65 rows
+         ("vanilla", 7, 1, True), ("vanilla", 7, 1, False), ("vanilla", 19, 1, True), ("betaH", 1, 1, True),
+         ("iwae", 13, 1, True), ("betaH", 19, 2, False)]
 
 
 def _tag(a, b, s, d):
