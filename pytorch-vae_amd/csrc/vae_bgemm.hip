@@ -463,15 +463,7 @@ __global__ void __launch_bounds__(BG_T, NSTG >= 4 ? 1 : 2) bwg_kernel(const WgPa
 
 template <int AM, int EM>
 int bgemm_go(GemmParams p, void* ws, long ws_bytes, hipStream_t st) {
-  int kmax = p.K;
-  if (AM == A_CONVT) {
-    kmax = 0;
-    for (int ph = 0; ph < p.nphase; ++ph) {
-      const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
-      kmax = k > kmax ? k : kmax;
-    }
-  }
-  const int ktiles = kmax / BG_K;
+  const int ktiles = phase_kmax(p, AM) / BG_K;
   const long tiles = (long)((p.M + BG_M - 1) / BG_M) * (p.N / BG_N) * p.nphase;
   // ring depth (bg_ops): two stages at two workgroups per CU for grids of >= two rounds of CUs,
   // else four stages at one per CU, K split until the tiles cover the CUs (>= 4 K-steps a slice)
@@ -512,15 +504,7 @@ bool bgemm_ok(const GemmParams& p, int am, int em) {
   if (p.gc % BG_K || p.N % BG_N || p.out_ld % 8 || p.b_ld % 8) return false;
   if (((uintptr_t)p.a_ptr | (uintptr_t)p.b_ptr | (uintptr_t)p.out) & 15) return false;
   if (em == E_BNBWD && p.epi_xf.kind != VAE_X_NONE && (((uintptr_t)p.epi_xf.aux & 15) || p.epi_xf.channels % 8)) return false;
-  int kmax = p.K;
-  if (am == A_CONVT) {
-    kmax = 0;
-    for (int ph = 0; ph < p.nphase; ++ph) {
-      const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
-      kmax = k > kmax ? k : kmax;
-    }
-  }
-  const double flops = 2.0 * p.M * p.N * (double)kmax * p.nphase;      // (upper bound over phases)
+  const double flops = 2.0 * p.M * p.N * (double)phase_kmax(p, am) * p.nphase;      // (upper bound over phases)
   return flops >= kBgMinFlops;
 }
 

@@ -1025,8 +1025,6 @@ inline bool al16(const void* ptr) { return ((uintptr_t)ptr & 15u) == 0; }
 
 }  // namespace
 
-bool c3_enabled() { return true; }
-
 bool c3_shape_ok(int n, int h, int w, int p, int q, int r, int stride, int pad, int C, int N) {
   return n > 0 && h == 16 && w == 16 && p == 16 && q == 16 && r == 3 && stride == 1 && pad == 1 && C % 32 == 0 &&
          C >= 32 && N % 128 == 0 && N > 0 && (long)n * 256 * (C > N ? C : N) * 2 < (1l << 31);

@@ -62,7 +62,5 @@ struct P1Args {
 };
 bool p1_shape_ok(long M, int C, int N);
 int p1_launch(const P1Args& a, hipStream_t st);
-// VAE_NO_C3=1 keeps these convolutions on the conv-GEMM (A/B timing)
-bool c3_enabled();
 
 }  // namespace vae

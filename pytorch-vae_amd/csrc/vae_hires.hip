@@ -552,7 +552,7 @@ int hires_convT_bwd_launch(const vae_conv_args* a, hipStream_t st) {
 // Both gradients of a ConvTranspose2d in one call (vaehip.h): the fused full-resolution kernel when
 // the layer is the decoder's last one, else vae_convT2d_bwd_data then vae_convT2d_bwd_filter.
 extern "C" int vae_convT2d_bwd(const vae_conv_args* a, void* stream) {
-  if (!vae::geom_ok(a, "convT2d_bwd")) return VAE_E_BADARG;
+  if (int rc = vae::check_geom(a, "convT2d_bwd")) return rc;
   if (!a->dy || !a->x || !a->dw || !a->dx || !a->wt) return vae::fail(VAE_E_BADARG, "convT2d_bwd: null tensor");
   if (a->dtype == VAE_BF16) {
     int rc = vae::rgb_out_bwd_launch(a, (hipStream_t)stream);     // the VQ-VAE's output ConvT(C -> 3)

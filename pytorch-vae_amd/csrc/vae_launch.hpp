@@ -4,6 +4,7 @@
 #include "vae_fgemm.hpp"
 #include "vae_cgemm.hpp"
 #include "vae_bgemm.hpp"
+#include "vae_gemm_desc.hpp"
 #include <stdlib.h>
 
 #ifdef VAE_PROBE
@@ -30,11 +31,6 @@ inline long cg_static_bytes(int bm, int bn) {
   const long loop = 2l * (bm + bn) * (bk + 8) * 2, epi = (long)bm * (bn + 4) * 4;
   const int wn = bn >= 2 * bm ? 4 : (bm >= 2 * bn ? 1 : 2);
   return (loop > epi ? loop : epi) + (4 / wn) * 2l * bn * 4 + 256;
-}
-
-inline vae_xform sanitize(vae_xform x) {
-  if (x.channels <= 0) x.channels = 1;
-  return x;
 }
 
 inline bool xf_ok(const vae_xform& x, const char* what) {
@@ -66,28 +62,12 @@ inline bool epi_ok(const vae_xform& x, const char* what) {
   return true;
 }
 
-// Phase tap tables of a transposed conv (or conv dgrad) with stride S, kernel R, padding P:
-// output coordinate o of phase ph = o % S receives taps r with (ph + P - r) % S == 0.
-inline bool make_taps(GemmParams& p, int S, int R, int P) {
-  if (S < 1 || S > 2) return false;
-  for (int ph = 0; ph < S; ++ph) {
-    const int first = ((ph + P) % S + S) % S;       // smallest r with (ph + P - r) % S == 0
-    const int n = first < R ? (R - 1 - first) / S + 1 : 0;
-    if (n < 1 || n > 4) return false;
-    p.tap0[ph] = first;
-    p.ntap_h[ph] = n; p.ntap_w[ph] = n;
-    p.tap_d[ph] = (ph + P - first) / S;
-  }
-  return true;
-}
-
 // The optional BatchNorm finalisation a producing call carries (vae_conv_args.bn_finalize):
 // validated up front, launched right after the GEMM (see vaehip.h; an in-kernel last-workgroup
 // variant measured slower: every workgroup then needs an agent-scope release, and the extra
 // epilogue code and LDS lowered the GEMMs' occupancy).
-inline int check_finalize(const vae_bn_args* f, const uint32_t* counter, const char* what) {
+inline int check_finalize(const vae_bn_args* f, const char* what) {
   if (!f) return VAE_OK;
-  (void)counter;
   if (f->mode != 0 && f->mode != 1) return fail(VAE_E_BADARG, "%s: fused finalisation mode %d", what, f->mode);
   if (!f->table || f->xf.channels <= 0 || !f->xf.sum || !f->xf.sumsq || !f->xf.gamma || !f->xf.beta || f->xf.count <= 0.f ||
       (f->mode == 1 && (!f->xf.dgamma || !f->xf.dbeta)) || f->xf.reps > BNF_LANES * BNF_PER)
@@ -98,15 +78,6 @@ inline int check_finalize(const vae_bn_args* f, const uint32_t* counter, const c
 inline int then_finalize(int rc, const vae_bn_args* f, hipStream_t st) {
   if (rc || !f) return rc;
   return bn_finalize_launch(f, st);
-}
-
-inline GemmParams base_params() {
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.ksplit = 1; p.nphase = 1; p.ones_col = -1; p.gs = 1; p.samples = 1; p.gr = 1;
-  p.a_xf.channels = 1; p.b_xf.channels = 1; p.epi_xf.channels = 1; p.res_xf.channels = 1;
-  p.ntap_h[0] = p.ntap_h[1] = p.ntap_w[0] = p.ntap_w[1] = 1;
-  return p;
 }
 
 // Elements a tensor operand spans (the buffer-resource extent; aux tensors are shaped alike).
@@ -123,6 +94,42 @@ inline long b_elems(const GemmParams& p) {
   if (BMD == B_NK) return (long)(p.N - 1) * p.b_ld + p.K;
   const long rows = p.b_taps ? (long)p.gc * p.gr * p.gr : p.K;   // B_KN
   return (rows - 1) * p.b_ld + (p.ones_col >= 0 ? p.N - 1 : p.N);
+}
+
+// GEMM depth the K-tile counts are planned for: K, or for the phase gather (am == A_CONVT) the
+// deepest phase's taps x channels.
+inline int phase_kmax(const GemmParams& p, int am) {
+  if (am != A_CONVT) return p.K;
+  int kmax = 0;
+  for (int ph = 0; ph < p.nphase; ++ph) {
+    const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
+    kmax = k > kmax ? k : kmax;
+  }
+  return kmax;
+}
+
+// Output-tensor extent (elements) the epilogue's aux operand spans: rows of the phase grid or
+// plain rows, times the row pitch.
+inline long out_elems(const GemmParams& p) {
+  if (p.out_phase) return (long)p.gn * p.gho * p.gwo * p.out_ld;
+  return (long)p.M * p.out_ld;
+}
+
+// The buffer-resource extents of a launch by `kernel`: ab / bb bytes of the A / B operands, ob
+// bytes the epilogue writes (0: the launcher sets no limit on them), aux bytes of the out-shaped
+// aux tensor.  Buffer addressing needs each checked size below 2 GiB.
+inline int set_extents(GemmParams& p, const char* kernel, long ab, long bb, long ob, long aux, const char* out_note) {
+  constexpr long lim = 1l << 31;
+  if (ab <= 0 || bb <= 0 || ab >= lim || bb >= lim)
+    return fail(VAE_E_UNSUPPORTED, "%s: operand of %ld / %ld bytes (buffer addressing needs < 2 GiB)", kernel, ab, bb);
+  if (ob >= lim) return fail(VAE_E_UNSUPPORTED, "%s: output of %ld bytes%s", kernel, ob, out_note);
+  p.a_bytes = (uint32_t)ab;
+  p.b_bytes = (uint32_t)bb;
+  p.out_aux_bytes = (uint32_t)aux;
+#ifdef VAE_PROBE
+  p.probe = vae_probe_buffer();
+#endif
+  return VAE_OK;
 }
 
 inline bool aligned(const void* ptr, int bytes) { return ((uintptr_t)ptr & (uintptr_t)(bytes - 1)) == 0; }
@@ -295,30 +302,15 @@ inline void launch_shape(const GemmParams& p, Tile t, hipStream_t st) {
 }
 #undef VAE_TILE_CASE
 
-// Output-tensor extent (elements) the epilogue's aux operand spans: rows of the phase grid or
-// plain rows, times the row pitch.
-inline long out_elems(const GemmParams& p) {
-  if (p.out_phase) return (long)p.gn * p.gho * p.gwo * p.out_ld;
-  return (long)p.M * p.out_ld;
-}
-
 template <class T, class TA, class TB, int AM, int BMD, int EM, bool DYA, bool DYB>
 inline int launch_tiled(GemmParams p, Tile t, hipStream_t st) {
-  const long ab = a_elems<AM>(p) * (long)sizeof(TA), bb = b_elems<BMD>(p) * (long)sizeof(TB);
-  if (ab <= 0 || bb <= 0 || ab >= (1l << 31) || bb >= (1l << 31))
-    return fail(VAE_E_UNSUPPORTED, "igemm: operand of %ld / %ld bytes (buffer addressing needs < 2 GiB)", ab, bb);
-  p.a_bytes = (uint32_t)ab;
-  p.b_bytes = (uint32_t)bb;
-  if (EM != E_ACC && EM != E_REPARAM) {
-    const long ob = out_elems(p) * (long)(p.out_f32 ? 4 : sizeof(T));
-    if (ob >= (1l << 31)) return fail(VAE_E_UNSUPPORTED, "igemm: output of %ld bytes (needs < 2 GiB)", ob);
-    p.out_aux_bytes = (uint32_t)(out_elems(p) * (long)sizeof(T));
-  }
+  const bool tensor_out = EM != E_ACC && EM != E_REPARAM;
+  const long oe = tensor_out ? out_elems(p) : 0;
+  if (int rc = set_extents(p, "igemm", a_elems<AM>(p) * (long)sizeof(TA), b_elems<BMD>(p) * (long)sizeof(TB),
+                           oe * (long)(p.out_f32 ? 4 : sizeof(T)), oe * (long)sizeof(T), " (needs < 2 GiB)"))
+    return rc;
   if ((!DYA && p.a_xf.kind == VAE_X_BN_DY) || (!DYB && p.b_xf.kind == VAE_X_BN_DY))
     return fail(VAE_E_UNSUPPORTED, "igemm: BN_DY transform on an operand this op does not support");
-#ifdef VAE_PROBE
-  p.probe = vae_probe_buffer();
-#endif
   // packed (vector) staging per operand: an operand that cannot be packed (the NCHW image, a
   // 3-channel tensor or weight matrix) no longer drags the other one onto the per-element path
   const bool va = operand_vec<AM>(p, p.a_ptr, p.a_xf, (int)sizeof(TA));
@@ -342,43 +334,27 @@ inline int launch_tiled(GemmParams p, Tile t, hipStream_t st) {
 // Shapes fgemm_kernel takes: k-contiguous weights (B_NK), gathered tensors with C % 32 == 0 (a
 // 32-deep k-step stays inside one tap), 16-byte aligned rows, packed BatchNorm channels.
 template <int AM, int BMD, int EM>
-inline bool fgemm_ok(const GemmParams& p, int esize_a, int esize_b) {
+inline bool fgemm_ok(const GemmParams& p) {
   if constexpr (BMD != B_NK || AM == A_KM || EM == E_ACC) return false;
-  if (p.g_nchw || p.ones_col >= 0) return false;
   // Measured (profiles/r1_v2_kernel_breakdown.txt): direct fragments win on the deep-K Linear
   // shapes (fc_mu||fc_var 9.7 -> 4.0 us) but lose on the conv / convT ones, whose blocks run two
   // residency rounds of latency-bound phases; those stay on the LDS-staged kernel.
-  if (AM == A_CONV || AM == A_CONVT) {
-    return false;
-  } else {
-    if (p.K % 32 || p.a_ld % 8) return false;
-  }
-  if (p.b_ld % 8 || (p.K % 32 && AM != A_CONVT)) return false;
+  if constexpr (AM == A_CONV || AM == A_CONVT) return false;
+  if (p.g_nchw || p.ones_col >= 0) return false;
+  if (p.K % 32 || p.a_ld % 8 || p.b_ld % 8) return false;
   if (!aligned(p.a_ptr, 16) || !aligned(p.b_ptr, 16)) return false;
   if (p.a_xf.kind == VAE_X_BN_DY && !aligned(p.a_xf.aux, 16)) return false;
   if (bn_kind(p.a_xf) && p.a_xf.channels % 8) return false;
-  (void)esize_a; (void)esize_b;
   return true;
 }
 
 template <class T, class TA, int AM, int EM, bool DYA>
 inline int launch_fgemm(GemmParams p, void* ws, long ws_bytes, hipStream_t st) {
   constexpr int BM = 32, BN = 32;
-  const long ab = a_elems<AM>(p) * (long)sizeof(TA), bb = b_elems<B_NK>(p) * (long)sizeof(T);
-  if (ab <= 0 || bb <= 0 || ab >= (1l << 31) || bb >= (1l << 31))
-    return fail(VAE_E_UNSUPPORTED, "fgemm: operand of %ld / %ld bytes (buffer addressing needs < 2 GiB)", ab, bb);
-  p.a_bytes = (uint32_t)ab;
-  p.b_bytes = (uint32_t)bb;
-  if (EM != E_REPARAM) p.out_aux_bytes = (uint32_t)(out_elems(p) * (long)sizeof(T));
-  int kmax = p.K;
-  if (AM == A_CONVT) {
-    kmax = 0;
-    for (int ph = 0; ph < p.nphase; ++ph) {
-      const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
-      kmax = k > kmax ? k : kmax;
-    }
-  }
-  const int steps = (kmax + 31) / 32;
+  if (int rc = set_extents(p, "fgemm", a_elems<AM>(p) * (long)sizeof(TA), b_elems<B_NK>(p) * (long)sizeof(T), 0,
+                           EM != E_REPARAM ? out_elems(p) * (long)sizeof(T) : 0, ""))
+    return rc;
+  const int steps = (phase_kmax(p, AM) + 31) / 32;
   const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.nphase;
   // split-K over workgroups (slabs + igemm_finalize) until ~2 workgroups per CU, >= 4 k-steps
   // per workgroup (one per wave)
@@ -391,9 +367,6 @@ inline int launch_fgemm(GemmParams p, void* ws, long ws_bytes, hipStream_t st) {
   if (int rc = split_fits(&split, 0, p, ws, ws_bytes, "fgemm split-K")) return rc;
   p.ksplit = split;
   p.slab = split > 1 ? static_cast<float*>(ws) : nullptr;
-#ifdef VAE_PROBE
-  p.probe = vae_probe_buffer();
-#endif
   const dim3 grid((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, p.nphase * p.ksplit);
   const size_t lds = (size_t)(tab_floats(p.a_xf, false) + (EM == E_BNBWD ? tab_floats(p.epi_xf, true) : 0)) * 4;
   VAE_LAUNCH((fgemm_kernel<T, TA, BM, BN, AM, EM, DYA>), grid, dim3(256), lds, st, p);
@@ -411,22 +384,14 @@ inline int launch(int dtype, bool a_f32, bool b_f32, GemmParams p, int split_req
   if (p.M <= 0 || p.N <= 0) return VAE_OK;
   finish_divs(p);
   if constexpr (BMD == B_NK && AM != A_KM && EM != E_ACC) {
-    if (!a_f32 && !b_f32 && split_req <= 0 && !p.det && fgemm_ok<AM, BMD, EM>(p, 0, 0)) {
+    if (!a_f32 && !b_f32 && split_req <= 0 && !p.det && fgemm_ok<AM, BMD, EM>(p)) {
       if (dtype == VAE_F32) return launch_fgemm<float, float, AM, EM, DYA>(p, ws, ws_bytes, st);
       if (dtype == VAE_BF16) return launch_fgemm<__bf16, __bf16, AM, EM, DYA>(p, ws, ws_bytes, st);
     }
   }
   const Tile t = pick_tile(p.M, p.N, p.nphase);
   const int bk = dtype == VAE_F32 ? 32 : 64;
-  int kmax = p.K;
-  if (AM == A_CONVT) {
-    kmax = 0;
-    for (int ph = 0; ph < p.nphase; ++ph) {
-      const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
-      kmax = k > kmax ? k : kmax;
-    }
-  }
-  const int ktiles = (kmax + bk - 1) / bk;
+  const int ktiles = (phase_kmax(p, AM) + bk - 1) / bk;
   const long blocks = (long)((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) * p.nphase;
   if (p.det && dtype != VAE_F32) return fail(VAE_E_UNSUPPORTED, "deterministic reductions need dtype VAE_F32");
   // deterministic weight gradients: K slices to a slab (<= 64 MB) summed by the finalize instead
@@ -547,16 +512,49 @@ __global__ void __launch_bounds__(256) flip_weights_kernel(const __bf16* w, __bf
   }
 }
 
-inline int flip_weights_launch(const __bf16* w, __bf16* wf, int K, int R, int C, hipStream_t st, int flip = 1) {
+inline int flip_weights_launch(const __bf16* w, __bf16* wf, int K, int R, int C, hipStream_t st, int flip) {
   const dim3 grid((C + 31) / 32, (K + 31) / 32, R * R);
   VAE_LAUNCH(flip_weights_kernel, grid, dim3(256), 0, st, w, wf, K, R * R, C, flip);
   return check_launch("flip_weights");
 }
 
+// The bf16 weight copy with the outer axes swapped that a data-path route reads instead of wt:
+// the caller's (`given`: wt_t, refreshed with the weights), else one staged in the last bytes of
+// the workspace (256-byte floor), the front staying the route's own.
+struct StagedWeights {
+  const void* ptr;     // NULL: no copy to be had (none given and no workspace)
+  long slab_bytes;     // workspace bytes in front of the copy
+  long tail;           // bytes staged; 0: the caller's copy
+};
+inline StagedWeights staged_weights(const vae_conv_args* a, const void* given) {
+  StagedWeights s = {given, a->workspace_bytes, 0};
+  if (!given && a->workspace) {
+    s.tail = (long)a->k * a->r * a->r * a->c * 2;
+    s.slab_bytes = ((a->workspace_bytes - s.tail) / 256) * 256;
+    if (s.slab_bytes < 0) s.slab_bytes = 0;
+    s.ptr = static_cast<char*>(a->workspace) + s.slab_bytes;
+  }
+  return s;
+}
+// Run the route (`go`) with the copy in place: a staged one is counted in the workspace need,
+// checked against the workspace and written first, from wt [K][r][r][C] (flip: taps reversed).
+template <class F>
+inline int with_staged_weights(const StagedWeights& s, const vae_conv_args* a, int K, int C, int flip, const char* what,
+                               hipStream_t st, F&& go) {
+  return with_ws_tail(s.tail, [&]() -> int {
+    if (s.tail) {
+      if (!ws_fits(s.tail, a->workspace_bytes, what)) return VAE_E_BADARG;
+      if (int rc = flip_weights_launch(static_cast<const __bf16*>(a->wt), static_cast<__bf16*>(const_cast<void*>(s.ptr)),
+                                       K, a->r, C, st, flip)) return rc;
+    }
+    return go();
+  });
+}
+
 // ------------------------------------------------------------------ bf16 conv-GEMM (vae_cgemm.hpp)
 // Eligible: bf16 NHWC operands with channel counts % 8 (16-byte chunks never straddle a tap),
 // 16-byte aligned tensors, k-contiguous weight rows, and a transform / epilogue pair the kernel
-// is instantiated for.  VAE_NO_CGEMM=1 keeps everything on the generic kernel (A/B timing).
+// is instantiated for.
 inline bool cg_ok(const GemmParams& p, int em) {
   if (p.g_nchw || p.ones_col >= 0 || p.gc % 8 || p.N % 8 || p.out_ld % 8 || p.b_ld % 8) return false;
   if (!aligned(p.a_ptr, 16) || !aligned(p.b_ptr, 16) || !aligned(p.out, 16)) return false;
@@ -581,8 +579,6 @@ struct CgTile { int bm, bn; };
 // K is split while a launch has fewer than kCgSplitWg workgroups per CU (swept in round 5,
 // profiles/r5_notes.md: 1 / 3 / 4 and 2 / 3 measured slower on the VanillaVAE step)
 constexpr int kCgMinWg = 2, kCgSplitWg = 1;
-inline int cg_minwg() { return kCgMinWg; }
-inline int cg_splitwg() { return kCgSplitWg; }
 
 // Largest tile that still gives every CU ~2 workgroups; split-K (slabs + igemm_finalize) when
 // even the smallest leaves the chip half empty and K is deep.  xform: the gathered operand is
@@ -597,7 +593,7 @@ inline CgTile cg_pick(long M, long N, int nphase, long table_bytes = 0, bool xfo
     if (t.bm > 32 && M < t.bm) continue;
     if (t.bn > 32 && N < t.bn) continue;
     if (t.bm == 128 && t.bn == 32 && tile_blocks(M, N, nphase, Tile{64, 32}) < (xform ? 4 : 8) * kCUs) continue;
-    if (tile_blocks(M, N, nphase, Tile{t.bm, t.bn}) >= (long)cg_minwg() * kCUs) return t;
+    if (tile_blocks(M, N, nphase, Tile{t.bm, t.bn}) >= (long)kCgMinWg * kCUs) return t;
   }
   return CgTile{32, 32};
 }
@@ -606,8 +602,7 @@ template <int BM, int BN> constexpr int cg_bk() { return BM >= 128 ? 64 : 128; }
 
 template <int AM, int XA, int EM, int OR>
 inline void cg_launch_tile(const GemmParams& p, CgTile t, hipStream_t st) {
-  const size_t lds = (size_t)((XA == VAE_X_BN_ACT || XA == VAE_X_BN_DY ? 3 * tab_stride(p.a_xf.channels) : 0) +
-                              (EM == E_BNBWD ? 4 * tab_stride(p.epi_xf.channels) : 0)) * 4;
+  const size_t lds = (size_t)cg_table_bytes(p, EM);   // (XA == p.a_xf.kind: cg_launch's switch)
 #define VAE_CG_CASE(BM_, BN_) \
   if (t.bm == BM_ && t.bn == BN_) { \
     const unsigned nb = (unsigned)(((p.M + BM_ - 1) / BM_) * ((p.N + BN_ - 1) / BN_) * p.nphase * p.ksplit); \
@@ -628,17 +623,8 @@ template <int AM, int EM>
 inline int cg_launch(GemmParams p, int split_req, void* ws, long ws_bytes, hipStream_t st) {
   if (p.M <= 0 || p.N <= 0) return VAE_OK;
   finish_divs(p);
-  const long ab = a_elems<AM>(p) * 2, bb = (long)(p.N - 1) * p.b_ld * 2 + (long)p.b_ld * 2;
-  if (ab <= 0 || bb <= 0 || ab >= (1l << 31) || bb >= (1l << 31))
-    return fail(VAE_E_UNSUPPORTED, "cgemm: operand of %ld / %ld bytes (buffer addressing needs < 2 GiB)", ab, bb);
-  p.a_bytes = (uint32_t)ab;
-  p.b_bytes = (uint32_t)bb;
   const long ob = out_elems(p) * 2;
-  if (ob >= (1l << 31)) return fail(VAE_E_UNSUPPORTED, "cgemm: output of %ld bytes", ob);
-  p.out_aux_bytes = (uint32_t)ob;
-#ifdef VAE_PROBE
-  p.probe = vae_probe_buffer();
-#endif
+  if (int rc = set_extents(p, "cgemm", a_elems<AM>(p) * 2, (long)p.N * p.b_ld * 2, ob, ob, "")) return rc;   // (whole rows of B)
   // transform-free large layers (an operand the caller materialised): the LDS-DMA pipeline
   if (split_req <= 0 && bgemm_ok(p, AM, EM)) {
     const int rc = bgemm_launch(p, AM, EM, ws, ws_bytes, st);
@@ -649,19 +635,11 @@ inline int cg_launch(GemmParams p, int split_req, void* ws, long ws_bytes, hipSt
   const int bk = t.bm >= 128 ? 64 : 128;
   // tile order (vae_cgemm.hpp): m fastest when the weights outweigh the gathered input tensor
   p.m_fast = (long)p.b_bytes > (long)p.a_bytes ? 1 : 0;
-  int kmax = p.K;
-  if (AM == A_CONVT) {
-    kmax = 0;
-    for (int ph = 0; ph < p.nphase; ++ph) {
-      const int k = p.ntap_h[ph / p.gs] * p.ntap_w[ph % p.gs] * p.gc;
-      kmax = k > kmax ? k : kmax;
-    }
-  }
-  const int ktiles = (kmax + bk - 1) / bk;
+  const int ktiles = (phase_kmax(p, AM) + bk - 1) / bk;
   const long blocks = tile_blocks(p.M, p.N, p.nphase, Tile{t.bm, t.bn});
   int split = split_req > 0 ? split_req : 1;
-  if (split_req <= 0 && blocks < (long)cg_splitwg() * kCUs && ktiles >= 4) {
-    split = (int)((2 * (long)cg_splitwg() * kCUs + blocks - 1) / blocks);
+  if (split_req <= 0 && blocks < (long)kCgSplitWg * kCUs && ktiles >= 4) {
+    split = (int)((2 * (long)kCgSplitWg * kCUs + blocks - 1) / blocks);
     if (split > ktiles / 2) split = ktiles / 2;
   }
   if (int rc = split_fits(&split, split_req, p, ws, ws_bytes, "cgemm split-K")) return rc;
@@ -721,21 +699,11 @@ inline int column_sum_launch(int dtype, const void* dy, long rows, int C, float*
   return check_launch("column_sum");
 }
 
-}  // namespace
-}  // namespace vae
-
-namespace vae {
-namespace {
-inline bool geom_ok(const vae_conv_args* a, const char* what) {
-  if (!a) { fail(VAE_E_BADARG, "%s: null args", what); return false; }
-  if (a->n <= 0 || a->h <= 0 || a->w <= 0 || a->c <= 0 || a->k <= 0 || a->p <= 0 || a->q <= 0 || a->r <= 0 ||
-      a->stride <= 0 || a->pad < 0) {
-    fail(VAE_E_BADSHAPE, "%s: bad geometry", what); return false;
-  }
-  if (a->deterministic && a->dtype != VAE_F32) {
-    fail(VAE_E_UNSUPPORTED, "%s: deterministic reductions need dtype VAE_F32", what); return false;
-  }
-  return true;
+// After a weight-gradient launch (rc): db[k] += Σ dy, unless the launch took it along (`done`)
+inline int then_bias_grad(int rc, const vae_conv_args* a, bool done, hipStream_t st) {
+  if (rc || !a->db || done) return rc;
+  return column_sum_launch(a->dtype, a->dy, (long)a->n * a->p * a->q, a->k, a->db, st);
 }
+
 }  // namespace
 }  // namespace vae

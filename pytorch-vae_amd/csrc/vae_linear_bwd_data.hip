@@ -25,10 +25,9 @@ extern "C" int vae_linear_bwd_data(const vae_linear_args* a, void* stream) {
                                                   a->workspace_bytes, (hipStream_t)stream);
   }
   if (!a->dx) return fail(VAE_E_BADARG, "linear_bwd_data: dx");
-  p.epi_xf = sanitize(a->dx_epi); p.dgamma = a->dx_dgamma; p.dbeta = a->dx_dbeta;
-  p.sum_reps = a->sum_reps; p.sum_rstride = a->sum_rstride;
-  if (p.epi_xf.kind == VAE_X_BN_ACT && (!p.dgamma || !p.dbeta)) return fail(VAE_E_BADARG, "linear_bwd_data: dgamma/dbeta");
-  if (int rc = check_finalize(a->bn_finalize, a->bn_counter, "linear_bwd_data")) return rc;
+  if (int rc = bwd_epilogue(p, a->dx_epi, a->dx_dgamma, a->dx_dbeta, a->sum_reps, a->sum_rstride, nullptr, "linear_bwd_data"))
+    return rc;
+  if (int rc = check_finalize(a->bn_finalize, "linear_bwd_data")) return rc;
   return then_finalize(launch<A_DENSE, B_KN, E_BNBWD, false, false, true>(a->dtype, a->dy_f32 != 0, false, p, 0, a->workspace, a->workspace_bytes,
                                               (hipStream_t)stream), a->bn_finalize, (hipStream_t)stream);
 }

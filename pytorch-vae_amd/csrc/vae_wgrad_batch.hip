@@ -245,7 +245,7 @@ extern "C" int vae_conv_bwd_filter_batch(int32_t n, const int32_t* kinds, const 
     grouped[i] = false;
     WgParams w;
     bool closed = false;
-    const bool valid = geom_ok(a, "conv_bwd_filter_batch") && a->dy && a->x && a->dw &&
+    const bool valid = check_geom(a, "conv_bwd_filter_batch") == VAE_OK && a->dy && a->x && a->dw &&
                        xf_ok(a->dy_xf, "conv_bwd_filter_batch.dy") && xf_ok(a->x_xf, "conv_bwd_filter_batch.x");
     if (nl < kWg3Max && valid && conv_wg_params(a, kinds[i] == VAE_LAYER_CONVT2D, &w, &closed) && (!a->db || closed)) {
       const bool bu = w.u_xf.kind == VAE_X_BN_ACT || w.u_xf.kind == VAE_X_BN_DY;

@@ -3,6 +3,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from vae_amd import _lib as L
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "vaehip.h")
@@ -51,6 +53,26 @@ def test_activation_backward_epilogue_without_aux_is_rejected():
     a.dx_epi = L.Xform(kind=L.X_ACT, channels=8, slope=0.01)
     rc = lib.vae_conv2d_bwd_data(ctypes.byref(a), None)
     assert rc == -1 and b"aux" in lib.vae_last_error()
+
+
+@pytest.mark.parametrize("change,code,word", [(dict(dtype=L.BF16, deterministic=1), -4, b"deterministic"),
+                                              (dict(stride=0), -2, b"geometry")])
+def test_a_rejected_geometry_reports_its_own_reason(change, code, word):
+    """Every tensor pointer is set, so `null tensor` (VAE_E_BADARG) would name the wrong fault: the
+    code and text are those of the geometry check (vaehip.h VAE_E_UNSUPPORTED / VAE_E_BADSHAPE)."""
+    lib = L.load()
+    a = L.ConvArgs(dtype=L.F32, n=1, h=4, w=4, c=8, k=8, p=2, q=2, r=3, stride=2, pad=1)
+    a.x = a.wt = a.y = a.dy = a.dx = a.dw = 1 << 20
+    for f, v in change.items():
+        setattr(a, f, v)
+    for fn in ("vae_conv2d_fwd", "vae_conv2d_bwd_data", "vae_conv2d_bwd_filter", "vae_convT2d_fwd",
+               "vae_convT2d_bwd_data", "vae_convT2d_bwd_filter"):
+        assert getattr(lib, fn)(ctypes.byref(a), None) == code, fn
+        msg = lib.vae_last_error()
+        assert word in msg and b"null tensor" not in msg, (fn, msg)
+    out = ctypes.c_size_t(0)
+    assert lib.vae_conv2d_workspace_size(ctypes.byref(a), L.OP_FWD, ctypes.byref(out)) == code
+    assert word in lib.vae_last_error()
 
 
 def test_build_digest_names_the_sources():

@@ -165,9 +165,10 @@ def test_cgemm_convT2d_fwd(shape, give_wt_t):
     run_fwd(True, *shape, L.X_BN_ACT if shape[5] == 3 else L.X_ACT, give_wt_t=give_wt_t)
 
 
-def run_dgrad(transposed, N, cin, cout, hw, stride, R, pad, dy_kind, epi_kind, give_wt_t=False, seed=1):
+def run_dgrad(transposed, N, cin, cout, hw, stride, R, pad, dy_kind, epi_kind, give_wt_t=False, seed=1, odd_aux=False):
     """dx of conv2d / conv_transpose2d: dy (optionally through BN-backward on load), then the
-    epilogue's activation backward (+ Σg, Σg·x̂ for a BatchNorm-followed input)."""
+    epilogue's activation backward (+ Σg, Σg·x̂ for a BatchNorm-followed input).  odd_aux: the
+    stored pre-activation of x starts one element past a 16-byte boundary."""
     L = _L()
     g = torch.Generator().manual_seed(seed)
     if transposed:
@@ -205,6 +206,11 @@ def run_dgrad(transposed, N, cin, cout, hw, stride, R, pad, dy_kind, epi_kind, g
     else:
         gout = v
     gyd, ystd, xstd = nhwc(gy), nhwc(yst), nhwc(xst)
+    if odd_aux:
+        hold = torch.zeros(xstd.numel() + 8, device="cuda", dtype=torch.bfloat16)
+        hold[1:1 + xstd.numel()].copy_(xstd.flatten())
+        xstd = hold[1:1 + xstd.numel()]
+        assert xstd.data_ptr() % 16 == 2
     wd = w.permute(0, 2, 3, 1).contiguous().to("cuda", torch.bfloat16)
     dx = torch.empty(N, hw, hw, cin, device="cuda", dtype=torch.bfloat16)
     dgam = torch.zeros(cin, device="cuda"); dbet = torch.zeros(cin, device="cuda")
@@ -254,6 +260,16 @@ def test_cgemm_conv2d_bwd_data(shape, give_wt_t):
 def test_cgemm_conv2d_bwd_data_plain(epi):
     L = _L()
     run_dgrad(False, 8, 256, 256, 16, 1, 3, 1, L.X_NONE, L.X_NONE if epi == "none" else L.X_ACT)
+
+
+def test_conv2d_bwd_data_stride1_flipped_weights():
+    """The stride-1 data gradient the conv-GEMM refuses (here: a stored pre-activation that is not
+    16-byte aligned), with a workspace: a forward conv of dy over the flipped weight copy staged at
+    the workspace's end, on the generic kernel.  Two row tiles x one column tile, K = 144."""
+    from gpu_util import launched
+    L = _L()
+    log = launched(lambda: run_dgrad(False, 2, 16, 16, 8, 1, 3, 1, L.X_NONE, L.X_ACT, odd_aux=True))
+    assert "flip_weights_kernel" in log and "igemm_kernel" in log and "cgemm_kernel" not in log, log
 
 
 # ---------------------------------------------------------------------------------------------
@@ -366,10 +382,11 @@ class BN:
         return rnd(F.leaky_relu(z, SLOPE).float())
 
 
-def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, fp32=False):
+def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, fp32=False, odd_dy=False):
     """One bf16 weight-gradient call's arguments (kernel-side operands) and its fp64 reference.
     fp32: the parity mode's call instead (fp32 operands, nothing rounded to bf16, every partial sum
-    added in a fixed order: vae_conv_args.deterministic), against the same fp64 reference."""
+    added in a fixed order: vae_conv_args.deterministic), against the same fp64 reference.
+    odd_dy: the stored gradient starts 8 bytes past a 16-byte boundary."""
     L = _L()
     bf = (lambda t: t.float()) if fp32 else globals()["bf"]
     nhwc = (lambda t: t.permute(0, 2, 3, 1).contiguous().to("cuda", torch.float32)) if fp32 else globals()["nhwc"]
@@ -412,6 +429,11 @@ def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, se
     out.backward(dyp.double())
     want = w0.grad.permute(0, 2, 3, 1)                                 # native [a][r][s][b]
     xd, yd, gd = nhwc(xst), nhwc(yst), nhwc(gst)
+    if odd_dy:
+        hold = torch.zeros(gd.numel() + 8, device="cuda", dtype=gd.dtype)
+        hold[4:4 + gd.numel()].copy_(gd.flatten())
+        gd = hold[4:4 + gd.numel()]
+        assert gd.data_ptr() % 16 == 8
     dw = torch.zeros(want.shape, device="cuda")
     db = torch.zeros(cout, device="cuda")
     dgo = torch.zeros(cout, device="cuda"); dbo = torch.zeros(cout, device="cuda")
@@ -454,10 +476,10 @@ def check_wgrad(w):
         assert e_dg < 1e-5 and e_dbt < 1e-5
 
 
-def run_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3):
+def run_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, odd_dy=False):
     """One standalone bf16 weight-gradient call (its queried workspace given) against fp64."""
     L = _L()
-    w = prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed)
+    w = prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed, odd_dy=odd_dy)
     a, fn = w["a"], w["fn"]
     ws = give_workspace(a, fn)           # 4 bytes when the plan takes none
     L.call(fn, ctypes.byref(a), torch.cuda.current_stream().cuda_stream)
@@ -495,6 +517,15 @@ WGRAD_T = [  # N, cin, cout, hw (convT input), stride, R, pad
 def test_wgemm_convT2d_bn(shape):
     L = _L()
     run_wgrad(True, *shape, L.X_BN_ACT, L.X_BN_DY)
+
+
+def test_conv2d_bwd_filter_tap_tile_kernel():
+    """The 128 x 128 one-tap kernel (vae_wgrad.hpp) takes a bf16 weight gradient the weight-gradient
+    GEMM refuses (here: a gradient tensor that is not 16-byte aligned) with at least 64 channels on
+    both sides and 8192 output pixels: 8 x 32 x 32, 64 -> 64 (half a tile each way), one tile per
+    tap, 32 K slices of 256 pixels."""
+    L = _L()
+    _ran("wgrad_bf16_kernel", lambda: run_wgrad(False, 8, 64, 64, 32, 1, 3, 1, L.X_ACT, L.X_NONE, odd_dy=True))
 
 
 def test_wgemm_convT2d_vq_shape():
