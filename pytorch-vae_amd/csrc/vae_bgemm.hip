@@ -484,7 +484,7 @@ int bgemm_go(GemmParams p, void* ws, long ws_bytes, hipStream_t st) {
   const size_t lt = (size_t)BG_EPI + (EM == E_BNBWD ? (size_t)tab_floats(p.epi_xf, true) * 4 : 0);
   const size_t ops = (size_t)(nstg == 2 ? bg_ops<2>() : bg_ops<4>());
   const size_t lds = lt > ops ? lt : ops;
-  if (lds > (size_t)kLdsBytes) return kHeadFallback;
+  if (lds > (size_t)kLdsBytes) return kRouteDeclined;
   const unsigned nb = (unsigned)(tiles * split);
   if (nstg == 2) VAE_LAUNCH((bgemm_kernel<AM, EM, 2>), dim3(nb), dim3(BG_T), lds, st, p);
   else VAE_LAUNCH((bgemm_kernel<AM, EM, 4>), dim3(nb), dim3(BG_T), lds, st, p);

@@ -5,6 +5,6 @@
 
 namespace vae {
 bool bgemm_ok(const GemmParams& p, int am, int em);
-// kHeadFallback when the launch cannot take the shape after all (LDS budget); else a status
+// kRouteDeclined when the launch cannot take the shape after all (LDS budget); else a status
 int bgemm_launch(const GemmParams& p, int am, int em, void* ws, long ws_bytes, hipStream_t st);
 }  // namespace vae

@@ -14,19 +14,28 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 namespace vae {
 
-// ---------------------------------------------------------------- error state (host)
+// ---------------------------------------------------------------- error state (host, vae_runtime.hip)
 void set_error(const char* fmt, ...);
 int fail(int code, const char* fmt, ...);
 int check_launch(const char* what);
-// vae_bn_finalize as a host call (validation + launch); used by fused-finalisation fallbacks
+// vae_bn_finalize as a host call (validation + launch, vae_bn.hip); used by fused-finalisation
+// fallbacks
 int bn_finalize_launch(const vae_bn_args* a, hipStream_t stream);
-// returned by a fast-path launcher whose preconditions do not hold (the caller falls back)
-constexpr int kHeadFallback = 0x7fff0001;
+// returned by the launcher of a special-shape kernel that lives in a unit of its own (vae_rgb.hpp,
+// vae_hires.hpp, vae_bgemm.hpp) when the call is not its shape: the entry point runs its next route
+constexpr int kRouteDeclined = 0x7fff0001;
+
+// Workgroups of a grid-stride streaming launch over n elements
+inline int grid_for(long n, int per_block = 256, int max_blocks = 2048) {
+  long b = (n + per_block - 1) / per_block;
+  if (b < 1) b = 1;
+  return (int)(b > max_blocks ? max_blocks : b);
+}
 
 // ---------------------------------------------------------------- deterministic reductions
 // A call made with `deterministic` set writes every cross-workgroup partial sum it would have
 // added with a float atomic to its own row of a workspace slab instead, and one ordered pass
-// (ordered_sum_launch, vae_misc.hip) adds the rows in a fixed order:
+// (ordered_sum_launch, vae_runtime.hip) adds the rows in a fixed order:
 //   output (g, c), g < groups, c < cols, sums slab rows [g*rpg, (g+1)*rpg) in ascending order,
 //   each row at column (c / cw) * hstride + c % cw + f * fstride for f = 0 .. folds-1, and adds the
 //   total into dst[c / cw][g * gstride + c % cw] (one thread owns each output: no atomics).

@@ -1,12 +1,9 @@
 // C-ABI entry points of ConvTranspose2d (decoder blocks, models/vanilla_vae.py:50-55, :65-70).
 #include "vae_launch.hpp"
 #include "vae_wgrad.hpp"
+#include "vae_hires.hpp"
 
 using namespace vae;
-
-namespace vae {
-int hires_convT_fwd_launch(const vae_conv_args* a, hipStream_t st);   // vae_hires.hip
-}
 
 // y[n,ho,wo,k] = Σ_{r,s,c: ho = h*S-P+r} xf(x)[n,h,w,c] · W[c][r][s][k] + b[k]   (phase GEMMs)
 extern "C" int vae_convT2d_fwd(const vae_conv_args* a, void* stream) {
@@ -23,7 +20,7 @@ extern "C" int vae_convT2d_fwd(const vae_conv_args* a, void* stream) {
   if (a->dtype == VAE_BF16) {
     // the decoder's full-resolution last ConvTranspose2d (32 -> 32, 32x32 -> 64x64)
     const int rc = hires_convT_fwd_launch(a, st);
-    if (rc != kHeadFallback) return rc;
+    if (rc != kRouteDeclined) return rc;
     // bf16 conv-GEMM: B = the swapped-axes weight copy WT[k][r][s][c] (k-contiguous rows), taken
     // from the caller (wt_t, refreshed with the weights) or built at the end of the workspace
     const StagedWeights w = staged_weights(a, a->wt_t);

@@ -16,7 +16,7 @@ extern "C" int vae_conv2d_bwd_filter(const vae_conv_args* a, void* stream) {
   const bool closed = a->db && a->dy_xf.kind == VAE_X_BN_DY;   // Σdy from the BN sums
   if (a->dtype == VAE_BF16) {                                   // the VQ-VAE's input Conv2d(3 -> C, k4 s2)
     const int rc = rgb_in_wgrad_launch(a, st);
-    if (rc != kHeadFallback) return rc;
+    if (rc != kRouteDeclined) return rc;
   }
   // The VQ-VAE's residual stacks (16 x 16 grid, stride 1): image-group tiles of the 3x3 convs with
   // the halo patch staged once per image, and the pointwise ones (vae_c3.hip); both need a

@@ -1,7 +1,9 @@
-// Decoder head on MFMA (bf16 throughput mode): final_layer Conv2d(C->3, k3, s1, p1) + Tanh
-// (models/vanilla_vae.py:73-75, models/autoencoder.py:84-86), the reconstruction SSE of the ELBO
-// (vanilla_vae.py:140) and their backward, for C = 32 (the VAEs), 64 and 128 (the Autoencoder's
-// big_ae final layer, configs/big_ae.yaml).
+// The decoder head: final_layer Conv2d(C->3, k3, s1, p1) + Tanh (models/vanilla_vae.py:73-75,
+// models/autoencoder.py:84-86), the reconstruction SSE of the ELBO (vanilla_vae.py:140) and their
+// backward.  The four vae_head_* entry points are at the end of this file; each runs the MFMA
+// kernels below (bf16 throughput mode: C = 32 (the VAEs), 64 and 128 (the Autoencoder's big_ae
+// final layer, configs/big_ae.yaml) on 64-wide images) when head_mfma_ok holds, and the VALU
+// kernels of vae_head_valu.hpp for every other call.
 //
 // The layer has 3 output channels: as a GEMM over pixels its N is 3, so the forward pads N to
 // the 16 of one v_mfma_f32_16x16x32_bf16 (13/16 of the MFMA is wasted, and the MFMA is still far
@@ -29,6 +31,7 @@
 
 #include "vae_common.hpp"
 #include "vae_elbo.hpp"
+#include "vae_head_valu.hpp"
 
 namespace vae {
 namespace {
@@ -770,21 +773,22 @@ __global__ void __launch_bounds__(256) reduce_rows_kernel(const float* src, int 
   }
 }
 
-bool head_mfma_ok(const vae_head_args* a) {
+// The calls the MFMA kernels take (every other call runs the VALU route, vae_head_valu.hpp): bf16,
+// 64-wide images, 32 / 64 / 128 channels, 16-byte aligned tensors; `data`: the call computes the
+// data gradient, whose fused epilogue is BatchNorm+LReLU.
+bool head_mfma_ok(const vae_head_args* a, bool data) {
   return a->dtype == VAE_BF16 && (a->c == 32 || a->c == 64 || a->c == 128) && a->w == HW && a->h > 0 &&
          a->h % 4 == 0 && a->n > 0 &&
          ((uintptr_t)a->x & 15) == 0 && ((uintptr_t)a->recon & 15) == 0 && ((uintptr_t)a->target & 15) == 0 &&
-         (a->x_xf.kind == VAE_X_BN_ACT || a->x_xf.kind == VAE_X_ACT || a->x_xf.kind == VAE_X_NONE);
+         (a->x_xf.kind == VAE_X_BN_ACT || a->x_xf.kind == VAE_X_ACT || a->x_xf.kind == VAE_X_NONE) &&
+         (!data || a->dx_epi.kind == VAE_X_BN_ACT);
 }
-
-// XCD-aware tile order
-int head_xcd() { return 1; }
 
 HeadQ head_q(const vae_head_args* a) {
   HeadQ q;
   memset(&q, 0, sizeof(q));
   q.n = a->n; q.h = a->h; q.samples = a->samples > 0 ? a->samples : 1;   // (q.tiles: per kernel)
-  q.xcd = head_xcd();
+  q.xcd = 1;                           // XCD-aware tile order
   q.x = static_cast<const __bf16*>(a->x); q.xf = a->x_xf;
   if (q.xf.channels <= 0) q.xf.channels = a->c;
   q.wt = a->wt; q.bias = a->bias; q.target = a->target; q.recon = a->recon; q.sse = a->sse;
@@ -850,8 +854,6 @@ int head_bwd_go(const vae_head_args* a, HeadQ q, int gsl_max, hipStream_t st) {
   return rc;
 }
 
-}  // namespace
-
 // Persistent grid of the backward.  C = 32, swept on MI355X (B=64 step): 128 -> 78.7 us,
 // 192 -> 61.7, 256 -> 45.6, 512 -> 50.5, 1024 -> 61.4 (more blocks means more filter partials to
 // reduce and more halo re-reads; fewer leaves CUs idle).  Re-swept with the tile-ahead loads:
@@ -861,18 +863,16 @@ int head_bwd_go(const vae_head_args* a, HeadQ q, int gsl_max, hipStream_t st) {
 // C = 64 / 128: 64-channel slices of 2 image rows, two workgroups per CU — 512 workgroups, i.e.
 // 512 per slice (C = 64) or 256 per slice (C = 128).
 constexpr int kHeadGrid = 512;
-int head_grid() { return kHeadGrid; }
 
-// Entry points used by vae_misc.hip's C ABI for the bf16 MFMA path.
+// The MFMA route of the forward (head_mfma_ok(a, false) holds).
 int head_fwd_mfma_launch(const vae_head_args* a, hipStream_t st) {
-  if (!head_mfma_ok(a)) return kHeadFallback;       // caller falls back to the VALU kernels
   HeadQ q = head_q(a);
   switch (a->c) {
     case 32: q.tiles = q.n * (q.h / 4); VAE_LAUNCH((head_fwd_mfma<32, 4>), dim3(q.tiles), dim3(256), 0, st, q); break;
     case 64: q.tiles = q.n * (q.h / 4); VAE_LAUNCH((head_fwd_mfma<64, 4>), dim3(q.tiles), dim3(256), 0, st, q); break;
     default: {
       q.tiles = q.n * (q.h / 2);
-      const int grid = q.tiles < head_grid() ? q.tiles : head_grid();   // two workgroups per CU
+      const int grid = q.tiles < kHeadGrid ? q.tiles : kHeadGrid;   // two workgroups per CU
       VAE_LAUNCH((head_fwd_stream<128, 2>), dim3(grid), dim3(256), 0, st, q);
       break;
     }
@@ -880,18 +880,74 @@ int head_fwd_mfma_launch(const vae_head_args* a, hipStream_t st) {
   return check_launch("head_fwd_mfma");
 }
 
-// data / filter: which halves of the backward to run.  The filter half writes per-block partials
-// into the caller's workspace (when large enough) and reduces them into dw/db in fixed order.
+// The MFMA route of the backward (head_mfma_ok(a, data) holds).  data / filter: which halves to
+// run.  The filter half writes per-block partials into the caller's workspace (when large enough)
+// and reduces them into dw/db in fixed order.
 int head_bwd_mfma_launch(const vae_head_args* a, bool data, bool filter, hipStream_t st) {
-  if (!head_mfma_ok(a)) return kHeadFallback;
-  if (data && a->dx_epi.kind != VAE_X_BN_ACT) return kHeadFallback;   // the fused epilogue is BatchNorm+LReLU
   HeadQ q = head_q(a);
   q.data = data; q.filter = filter;
   switch (a->c) {
-    case 32: return head_bwd_go<32, 4, 32>(a, q, head_grid(), st);
-    case 64: return head_bwd_go<64, 2, 64>(a, q, head_grid(), st);
-    default: return head_bwd_go<64, 2, 128>(a, q, head_grid() / 2, st);
+    case 32: return head_bwd_go<32, 4, 32>(a, q, kHeadGrid, st);
+    case 64: return head_bwd_go<64, 2, 64>(a, q, kHeadGrid, st);
+    default: return head_bwd_go<64, 2, 128>(a, q, kHeadGrid / 2, st);
   }
 }
 
+}  // namespace
 }  // namespace vae
+
+using namespace vae;
+
+// Each entry point: the checks both routes share (head_setup), its own argument checks, then the
+// MFMA kernels when head_mfma_ok, else the VALU kernels of vae_head_valu.hpp.
+extern "C" int vae_head_fwd(const vae_head_args* a, void* stream) {
+  HeadP p;
+  int rc = head_setup(a, p, "head_fwd");
+  if (rc) return rc;
+  if (!a->sse) return fail(VAE_E_BADARG, "head_fwd: sse");
+  const hipStream_t st = (hipStream_t)stream;
+  if (head_mfma_ok(a, false)) return head_fwd_mfma_launch(a, st);
+  return head_fwd_valu(a, p, st);
+}
+
+extern "C" int vae_head_bwd_data(const vae_head_args* a, void* stream) {
+  HeadP p;
+  int rc = head_setup(a, p, "head_bwd_data");
+  if (rc) return rc;
+  if ((!a->coef && !a->grad_recon) || !a->dx) return fail(VAE_E_BADARG, "head_bwd_data: coef/grad_recon/dx");
+  if (p.epi.kind == VAE_X_BN_ACT && (!p.dgamma || !p.dbeta || !p.epi.aux)) return fail(VAE_E_BADARG, "head_bwd_data: BN epilogue");
+  if (p.epi.kind != VAE_X_NONE && !p.epi.aux) return fail(VAE_E_BADARG, "head_bwd_data: epilogue aux");
+  const hipStream_t st = (hipStream_t)stream;
+  if (head_mfma_ok(a, true)) return head_bwd_mfma_launch(a, true, false, st);
+  return head_bwd_data_valu(a, p, st);
+}
+
+extern "C" int vae_head_bwd_filter(const vae_head_args* a, void* stream) {
+  HeadP p;
+  int rc = head_setup(a, p, "head_bwd_filter");
+  if (rc) return rc;
+  if ((!a->coef && !a->grad_recon) || !a->dw) return fail(VAE_E_BADARG, "head_bwd_filter: coef/grad_recon/dw");
+  if (9 * a->c > 9 * HEAD_MAXC) return fail(VAE_E_UNSUPPORTED, "head_bwd_filter: channels");
+  const hipStream_t st = (hipStream_t)stream;
+  if (head_mfma_ok(a, false)) return head_bwd_mfma_launch(a, false, true, st);
+  return head_bwd_filter_valu(a, p, st);
+}
+
+// Both gradients in one call: one MFMA launch, or the two VALU entry points in turn; then the final
+// BatchNorm's backward table when the caller asks for it.
+extern "C" int vae_head_bwd(const vae_head_args* a, void* stream) {
+  HeadP p;
+  int rc = head_setup(a, p, "head_bwd");
+  if (rc) return rc;
+  if ((!a->coef && !a->grad_recon && !a->elbo) || !a->dx || !a->dw) return fail(VAE_E_BADARG, "head_bwd: coef/grad_recon/dx/dw");
+  if (p.epi.kind == VAE_X_BN_ACT && (!p.dgamma || !p.dbeta || !p.epi.aux)) return fail(VAE_E_BADARG, "head_bwd: BN epilogue");
+  if (head_mfma_ok(a, true)) {
+    rc = head_bwd_mfma_launch(a, true, true, (hipStream_t)stream);
+  } else {
+    if (a->elbo) return fail(VAE_E_UNSUPPORTED, "head_bwd: a fused ELBO needs the bf16 MFMA path");
+    if ((rc = vae_head_bwd_data(a, stream))) return rc;
+    rc = vae_head_bwd_filter(a, stream);
+  }
+  if (rc || !a->bn_finalize) return rc;
+  return bn_finalize_launch(a->bn_finalize, (hipStream_t)stream);     // the final BatchNorm's backward table
+}

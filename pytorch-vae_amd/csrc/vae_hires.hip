@@ -17,6 +17,7 @@
 //     whole 4 KB rows (16 B per lane).
 #include "vae_launch.hpp"
 #include "vae_rgb.hpp"
+#include "vae_hires.hpp"
 
 namespace vae {
 namespace {
@@ -494,8 +495,8 @@ bool hires_convT_ok(const vae_conv_args* a) {
 int hires_convT_fwd_launch(const vae_conv_args* a, hipStream_t st) {
   if (!hires_convT_ok(a) || !a->wt_t || ((uintptr_t)a->wt_t & 15) || ((uintptr_t)a->y & 15) || a->residual ||
       a->bn_finalize)
-    return kHeadFallback;
-  if (a->x_xf.kind == VAE_X_BN_ACT && !a->x_xf.table && !bn_fast_ok(a->x_xf)) return kHeadFallback;
+    return kRouteDeclined;
+  if (a->x_xf.kind == VAE_X_BN_ACT && !a->x_xf.table && !bn_fast_ok(a->x_xf)) return kRouteDeclined;
   HiresF q;
   memset(&q, 0, sizeof(q));
   q.n = a->n;
@@ -509,25 +510,25 @@ int hires_convT_fwd_launch(const vae_conv_args* a, hipStream_t st) {
 }
 
 
-// The fused backward of the layer (dgrad + wgrad); kHeadFallback when the shapes / transforms are
+// The fused backward of the layer (dgrad + wgrad); kRouteDeclined when the shapes / transforms are
 // not these kernels' (the caller then runs vae_convT2d_bwd_data and vae_convT2d_bwd_filter).
 int hires_convT_bwd_launch(const vae_conv_args* a, hipStream_t st) {
-  if (!hires_convT_ok(a) || !a->dy || !a->dx || !a->dw || !a->wt || a->residual || a->bn_finalize) return kHeadFallback;
+  if (!hires_convT_ok(a) || !a->dy || !a->dx || !a->dw || !a->wt || a->residual || a->bn_finalize) return kRouteDeclined;
   if (a->dy_xf.kind != VAE_X_BN_DY || a->dy_xf.channels != HC || a->dy_xf.table || !bn_fast_ok(a->dy_xf) ||
       !a->dy_xf.aux || ((uintptr_t)a->dy_xf.aux & 15) || ((uintptr_t)a->dy & 15) || ((uintptr_t)a->dx & 15) ||
       ((uintptr_t)a->wt & 15))
-    return kHeadFallback;
-  if (a->db && a->dy_xf.kind != VAE_X_BN_DY) return kHeadFallback;
+    return kRouteDeclined;
+  if (a->db && a->dy_xf.kind != VAE_X_BN_DY) return kRouteDeclined;
   const vae_xform& e = a->dx_epi;
   if (!(e.kind == VAE_X_NONE || (e.kind == VAE_X_ACT && e.aux == a->x) ||
         (e.kind == VAE_X_BN_ACT && e.aux == a->x && e.channels == HC && !e.table && bn_fast_ok(e) && a->dx_dgamma && a->dx_dbeta)))
-    return kHeadFallback;
-  if (a->x_xf.kind == VAE_X_BN_ACT && (a->x_xf.table || !bn_fast_ok(a->x_xf))) return kHeadFallback;
+    return kRouteDeclined;
+  if (a->x_xf.kind == VAE_X_BN_ACT && (a->x_xf.table || !bn_fast_ok(a->x_xf))) return kRouteDeclined;
   const int tiles = a->n * (HIN / IR);
   const int gmax = kHiresBwdGrid;
   const int grid = tiles < gmax ? tiles : gmax;
   const long need = (long)grid * NW * 4;
-  if (!a->workspace && !querying()) return kHeadFallback;
+  if (!a->workspace && !querying()) return kRouteDeclined;
   if (!ws_fits(need, a->workspace_bytes, "convT2d_bwd filter partials")) return VAE_E_BADARG;
   HiresB q;
   memset(&q, 0, sizeof(q));
@@ -556,9 +557,9 @@ extern "C" int vae_convT2d_bwd(const vae_conv_args* a, void* stream) {
   if (!a->dy || !a->x || !a->dw || !a->dx || !a->wt) return vae::fail(VAE_E_BADARG, "convT2d_bwd: null tensor");
   if (a->dtype == VAE_BF16) {
     int rc = vae::rgb_out_bwd_launch(a, (hipStream_t)stream);     // the VQ-VAE's output ConvT(C -> 3)
-    if (rc != vae::kHeadFallback) return rc;
+    if (rc != vae::kRouteDeclined) return rc;
     rc = vae::hires_convT_bwd_launch(a, (hipStream_t)stream);
-    if (rc != vae::kHeadFallback) return rc;
+    if (rc != vae::kRouteDeclined) return rc;
   }
   if (int rc = vae_convT2d_bwd_data(a, stream)) return rc;
   return vae_convT2d_bwd_filter(a, stream);

@@ -609,10 +609,34 @@ int latent_check_x(const vae_latent_args* a, const vae_xform& xf, const char* wh
   return VAE_OK;
 }
 
+// ------------------------------------------------------------------ reparameterization
+// z = mu + eps * exp(logvar / 2) as a launch of its own (vae_reparam_fwd): the stand-alone form
+// of what latent_dec_fwd_kernel fuses
+template <class T>
+__global__ void reparam_kernel(int rows, int samples, int D, const float* mulv, const float* eps, T* z) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)rows * D) return;
+  const int r = (int)(i / D), d = (int)(i - (long)r * D);
+  const int b = r / samples;
+  const float mu = mulv[(long)b * 2 * D + d], lv = mulv[(long)b * 2 * D + D + d];
+  z[i] = cvt<T>(fmaf(eps[i], expf(0.5f * lv), mu));
+}
+
 }  // namespace
 }  // namespace vae
 
 using namespace vae;
+
+extern "C" int vae_reparam_fwd(int32_t dtype, int32_t rows, int32_t samples, int32_t latent, const float* mulv,
+                               const float* eps, void* z, void* stream) {
+  if (!mulv || !eps || !z || rows <= 0 || latent <= 0 || samples <= 0) return fail(VAE_E_BADARG, "reparam_fwd: args");
+  const long n = (long)rows * latent;
+  const int grid = (int)((n + 255) / 256);
+  if (dtype == VAE_F32) VAE_LAUNCH(reparam_kernel<float>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, samples, latent, mulv, eps, (float*)z);
+  else if (dtype == VAE_BF16) VAE_LAUNCH(reparam_kernel<__bf16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, samples, latent, mulv, eps, (__bf16*)z);
+  else return fail(VAE_E_BADDTYPE, "reparam_fwd: dtype");
+  return check_launch("reparam_fwd");
+}
 
 extern "C" int vae_latent_fc_fwd(const vae_latent_args* a, void* stream) {
   if (int rc = latent_check(a, "latent_fc_fwd")) return rc;

@@ -628,7 +628,7 @@ inline int cg_launch(GemmParams p, int split_req, void* ws, long ws_bytes, hipSt
   // transform-free large layers (an operand the caller materialised): the LDS-DMA pipeline
   if (split_req <= 0 && bgemm_ok(p, AM, EM)) {
     const int rc = bgemm_launch(p, AM, EM, ws, ws_bytes, st);
-    if (rc != kHeadFallback) return rc;
+    if (rc != kRouteDeclined) return rc;
   }
   const CgTile t = cg_pick(p.M, p.N, p.nphase, cg_table_bytes(p, EM),
                            p.a_xf.kind == VAE_X_BN_ACT || p.a_xf.kind == VAE_X_BN_DY);

@@ -492,10 +492,10 @@ int rgb_out_fwd_launch(const vae_conv_args* a, const vae_recon_args* rc, hipStre
   float slope;
   if (!rgb_geom(a, true) || !rgb_act(a->x_xf, &slope) || !a->x || !a->wt || !a->bias || a->residual ||
       a->bn_finalize || a->y_sum || !al16(a->x))
-    return kHeadFallback;
+    return kRouteDeclined;
   if (!rc || rc->n != a->n || rc->c != 3 || rc->h != 2 * RG_H || rc->w != 2 * RG_H || (rc->ld != 0 && rc->ld != RG_CP) ||
       !rc->target || !rc->recon || (rc->dy && !al16(rc->dy)))
-    return kHeadFallback;
+    return kRouteDeclined;
   RgbFwd q;
   q.n = a->n;
   q.x = static_cast<const __bf16*>(a->x); q.slope = slope;
@@ -510,20 +510,20 @@ int rgb_out_bwd_launch(const vae_conv_args* a, hipStream_t st) {
   float slope, es = 1.f;
   if (!rgb_geom(a, true) || !rgb_act(a->x_xf, &slope) || !a->dy || !a->x || !a->wt || !a->dx || !a->dw ||
       a->dy_xf.kind != VAE_X_NONE || a->residual || a->bn_finalize || !al16(a->x) || !al16(a->dx) || !al16(a->dy))
-    return kHeadFallback;
+    return kRouteDeclined;
   // the data gradient's epilogue is the input's LeakyReLU backward (aux = x) or none, matching x_xf
   if (a->dx_epi.kind == VAE_X_ACT) {
-    if (a->dx_epi.aux != a->x || a->dx_epi.slope != slope) return kHeadFallback;
+    if (a->dx_epi.aux != a->x || a->dx_epi.slope != slope) return kRouteDeclined;
     es = slope;
   } else if (a->dx_epi.kind != VAE_X_NONE || slope != 1.f) {
-    return kHeadFallback;
+    return kRouteDeclined;
   }
   (void)es;
-  if (a->dw_inner != 3) return kHeadFallback;         // dW straight into the parameter's [c][4][4][3]
+  if (a->dw_inner != 3) return kRouteDeclined;         // dW straight into the parameter's [c][4][4][3]
   const int tiles = a->n * (RG_H / RG_TI);
   const int per = (tiles + kRgbGrid - 1) / kRgbGrid;
   const int grid = (tiles + per - 1) / per;
-  if (!a->workspace && !querying()) return kHeadFallback;
+  if (!a->workspace && !querying()) return kRouteDeclined;
   if (!ws_fits((long)grid * RG_SLAB * 4, a->workspace_bytes, "rgb_out_bwd partials")) return VAE_E_BADARG;
   RgbBwd q;
   q.n = a->n; q.tiles = tiles; q.per = per;
@@ -542,11 +542,11 @@ int rgb_out_bwd_launch(const vae_conv_args* a, hipStream_t st) {
 int rgb_in_wgrad_launch(const vae_conv_args* a, hipStream_t st) {
   if (!rgb_geom(a, false) || !a->dy || !a->x || !a->dw || a->dy_xf.kind != VAE_X_NONE || a->x_xf.kind != VAE_X_NONE ||
       !al16(a->dy) || ((uintptr_t)a->x & 7) || a->dw_inner != 3)
-    return kHeadFallback;
+    return kRouteDeclined;
   const int tiles = a->n * (RG_H / RG_TI);
   const int per = (tiles + kRgbGrid - 1) / kRgbGrid;
   const int grid = (tiles + per - 1) / per;
-  if (!a->workspace && !querying()) return kHeadFallback;
+  if (!a->workspace && !querying()) return kRouteDeclined;
   if (!ws_fits((long)grid * RG_SLAB * 4, a->workspace_bytes, "rgb_in_wgrad partials")) return VAE_E_BADARG;
   RgbIn q;
   q.n = a->n; q.tiles = tiles; q.per = per;
@@ -567,7 +567,7 @@ int rgb_in_wgrad_launch(const vae_conv_args* a, hipStream_t st) {
 extern "C" int vae_convT2d_fwd_recon(const vae_conv_args* a, const vae_recon_args* rc, void* stream) {
   if (!vae::geom_ok_rgb(a)) return vae::fail(VAE_E_BADARG, "convT2d_fwd_recon: bad geometry");
   const int r = vae::rgb_out_fwd_launch(a, rc, (hipStream_t)stream);
-  if (r != vae::kHeadFallback) return r;
+  if (r != vae::kRouteDeclined) return r;
   if (!a->y) return vae::fail(VAE_E_UNSUPPORTED, "convT2d_fwd_recon: shape not on the fused kernel and no y to stage");
   if (int e = vae_convT2d_fwd(a, stream)) return e;
   return vae_recon_fwd(rc, stream);

@@ -1,4 +1,4 @@
-// Launchers of the VQ-VAE RGB-end kernels (vae_rgb.hip).  Each returns kHeadFallback when the call
+// Launchers of the VQ-VAE RGB-end kernels (vae_rgb.hip).  Each returns kRouteDeclined when the call
 // is not the shape / transform its kernel takes (the caller then runs the general path).
 #pragma once
 #include "vae_common.hpp"

@@ -11,7 +11,12 @@
 // The reference's step (experiment.py:45-49) feeds the image straight into the first Conv2d
 // (models/vanilla_vae.py:84); the padding exists only so that the first layer runs on the packed
 // 16-byte GEMM operand path.  profiles/r3a: the three separate launches took 6.5 + 5.2 + 4.8 us.
+//
+// The stand-alone forms of its ranges live here too (vae_step_begin, vae_swap_axes), and the tail
+// of the step: vae_step_record.
 #include <algorithm>
+
+#include <math.h>
 
 #include "vae_common.hpp"
 
@@ -89,10 +94,28 @@ __global__ void __launch_bounds__(256) step_begin_ex_kernel(const StepBegin s) {
   static_cast<T*>(d.dst)[i] = j < d.c ? static_cast<const T*>(d.src)[r * d.c + j] : cvt<T>(0.f);
 }
 
+// vae_step_begin: the zeroing range alone
+__global__ void step_begin_kernel(f32x4* z, long n16, unsigned char* tail, int ntail, int* step) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (long)gridDim.x * blockDim.x)
+    z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (blockIdx.x == 0 && threadIdx.x < ntail) tail[threadIdx.x] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && step) *step += 1;
+}
+
 }  // namespace
 }  // namespace vae
 
 using namespace vae;
+
+extern "C" int vae_step_begin(void* zero, int64_t bytes, int32_t* step, void* stream) {
+  if (bytes < 0 || (bytes > 0 && !zero)) return fail(VAE_E_BADARG, "step_begin: args");
+  if (((uintptr_t)zero & 15) != 0) return fail(VAE_E_BADARG, "step_begin: zero region must be 16-B aligned");
+  const long n16 = bytes / 16;
+  const int ntail = (int)(bytes - n16 * 16);
+  VAE_LAUNCH(step_begin_kernel, dim3(grid_for(n16 > 0 ? n16 : 1)), dim3(256), 0, (hipStream_t)stream,
+                     (f32x4*)zero, n16, (unsigned char*)zero + n16 * 16, ntail, (int*)step);
+  return check_launch("step_begin");
+}
 
 extern "C" int vae_step_begin_ex(const vae_step_begin_args* a, void* stream) {
   if (!a || a->bytes < 0 || (a->bytes > 0 && !a->zero)) return fail(VAE_E_BADARG, "step_begin_ex: zero region");
@@ -162,4 +185,115 @@ extern "C" int vae_step_begin_ex(const vae_step_begin_args* a, void* stream) {
   if (a->dtype == VAE_BF16) VAE_LAUNCH(step_begin_ex_kernel<__bf16>, grid, dim3(256), 0, (hipStream_t)stream, s);
   else VAE_LAUNCH(step_begin_ex_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, s);
   return check_launch("step_begin_ex");
+}
+
+// ------------------------------------------------------------------ training-step record
+namespace {
+__global__ void __launch_bounds__(256) step_record_kernel(const vae_record_args a) {
+  kernarg_prefetch<(sizeof(vae_record_args) < 1024 ? sizeof(vae_record_args) : 1024)>();
+  __shared__ float pv[1024];
+  __shared__ float rv[2][256];
+  __shared__ int ri[2][256];
+  __shared__ int win[2];
+  const int tid = threadIdx.x;
+  if (tid < a.nterms) a.terms[tid] = a.src_terms[tid];
+  const float inv_s = 1.0f / (float)a.samples;
+  for (int b = tid; b < a.batch; b += 256) {
+    float v = 0.f;
+    for (int s = 0; s < a.samples; ++s) v += a.per_img[b * a.samples + s];
+    v *= inv_s;
+    pv[b] = v;
+    a.per[b] = v;
+  }
+  __syncthreads();
+  // first index of the maximum / minimum (ties -> lowest index, as the reference's strict '>'/'<')
+  float mx = -INFINITY, mn = INFINITY;
+  int imx = 0x7fffffff, imn = 0x7fffffff;
+  for (int b = tid; b < a.batch; b += 256) {
+    const float v = pv[b];
+    if (v > mx) { mx = v; imx = b; }
+    if (v < mn) { mn = v; imn = b; }
+  }
+  rv[0][tid] = mx; ri[0][tid] = imx; rv[1][tid] = mn; ri[1][tid] = imn;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) {
+      const float v1 = rv[0][tid + off], v0 = rv[0][tid];
+      const int i1 = ri[0][tid + off], i0 = ri[0][tid];
+      if (v1 > v0 || (v1 == v0 && i1 < i0)) { rv[0][tid] = v1; ri[0][tid] = i1; }
+      const float w1 = rv[1][tid + off], w0 = rv[1][tid];
+      const int j1 = ri[1][tid + off], j0 = ri[1][tid];
+      if (w1 < w0 || (w1 == w0 && j1 < j0)) { rv[1][tid] = w1; ri[1][tid] = j1; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    win[0] = rv[0][0] > a.best[0] ? ri[0][0] : -1;
+    win[1] = rv[1][0] < a.best[1] ? ri[1][0] : -1;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int b = win[k];
+    if (b < 0) continue;
+    float* di = k == 0 ? a.hi_img : a.lo_img;
+    float* dr = k == 0 ? a.hi_recon : a.lo_recon;
+    for (int e = tid; e < a.img_elems; e += 256) {
+      di[e] = a.img[(long)b * a.img_elems + e];
+      dr[e] = a.recon[(long)b * a.samples * a.img_elems + e];
+    }
+    if (tid == 0) { a.best[k] = rv[k][0]; a.at[2 * k] = a.step; a.at[2 * k + 1] = b; }
+  }
+}
+}  // namespace
+
+extern "C" int vae_step_record(const vae_record_args* a, void* stream) {
+  if (!a || a->batch <= 0 || a->batch > 1024 || a->samples <= 0 || a->img_elems <= 0 || a->nterms < 0 || a->nterms > 8 ||
+      (a->nterms && (!a->src_terms || !a->terms)) || !a->per_img || !a->per || !a->img || !a->recon || !a->best || !a->at ||
+      !a->hi_img || !a->hi_recon || !a->lo_img || !a->lo_recon)
+    return fail(VAE_E_BADARG, "step_record: args");
+  VAE_LAUNCH(step_record_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
+  return check_launch("step_record");
+}
+
+// ------------------------------------------------------------------ swapped-axes weight copies
+// dst[b][t][a] = bf16(src[a][t][b]) for up to VAE_SWAP_MAX tensors in one launch: the k-contiguous
+// B operands of the bf16 ConvTranspose2d forward / Conv2d data-gradient GEMMs (vaehip.h wt_t),
+// refreshed from the fp32 master right after the optimizer step.  One workgroup = one
+// kSwapT x kSwapT (64x64) (a, b) tile of one tap through a padded LDS tile, each lane moving an
+// element pair (swap_tile, vae_common.hpp).
+namespace {
+struct SwapBatch {
+  vae_swap_desc d[VAE_SWAP_MAX];
+  int tiles0[VAE_SWAP_MAX + 1];      // first workgroup of each descriptor
+  int count;
+};
+
+__global__ void __launch_bounds__(256) swap_axes_kernel(const SwapBatch sb) {
+  kernarg_prefetch<(sizeof(SwapBatch) < 1024 ? sizeof(SwapBatch) : 1024)>();
+  __shared__ float t[kSwapT][kSwapT + 1];
+  int i = 0;
+  while (i + 1 < sb.count && (int)blockIdx.x >= sb.tiles0[i + 1]) ++i;
+  swap_tile(sb.d[i], blockIdx.x - sb.tiles0[i], t);
+}
+}  // namespace
+
+extern "C" int vae_swap_axes(int32_t count, const vae_swap_desc* descs, void* stream) {
+  if (count <= 0) return VAE_OK;
+  if (count > VAE_SWAP_MAX || !descs) return fail(VAE_E_BADARG, "swap_axes: count %d (max %d)", count, VAE_SWAP_MAX);
+  SwapBatch sb;
+  memset(&sb, 0, sizeof(sb));
+  int tiles = 0;
+  for (int i = 0; i < count; ++i) {
+    const vae_swap_desc& d = descs[i];
+    if (!d.src || !d.dst || d.a <= 0 || d.b <= 0 || d.rs <= 0 || (d.src_dtype != VAE_F32 && d.src_dtype != VAE_BF16))
+      return fail(VAE_E_BADARG, "swap_axes: descriptor %d", i);
+    sb.d[i] = d;
+    sb.tiles0[i] = tiles;
+    tiles += swap_tiles(d);
+  }
+  sb.tiles0[count] = tiles;
+  sb.count = count;
+  VAE_LAUNCH(swap_axes_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, sb);
+  return check_launch("swap_axes");
 }

@@ -25,9 +25,9 @@ def base():
 def test_two_runs_give_the_same_table(base):
     assert sw.table(L, **SMALL) == base
     parts = {r.split()[0] for r in base}
-    assert parts == {"base", "ext", "linear"}
+    assert parts == {"base", "ext", "linear", "head"}
     fns = {r.split()[1] for r in base}
-    assert fns == set(sw.CONV_FNS + sw.LINEAR_FNS)
+    assert fns == set(sw.CONV_FNS + sw.LINEAR_FNS + sw.HEAD_FNS)
     assert any(" rc=0 need=0" in r for r in base) and any(" rc=0 need=" in r and " need=0" not in r for r in base)
     assert any(" rc=-" in r for r in base)                       # rejected calls carry their message
 

@@ -12,23 +12,10 @@ import ctypes
 import pytest
 import torch
 
+from gpu_util import launched
 from test_gpu_cgemm import run_dgrad, run_fwd
 
 pytestmark = pytest.mark.gpu
-
-
-def _launched(fn):
-    from vae_amd import _lib as L
-    lib = L.load()
-    lib.vae_launch_log(1)
-    try:
-        fn()
-    finally:
-        lib.vae_launch_log(0)
-    need = lib.vae_launch_log_names(None, 0)
-    buf = ctypes.create_string_buffer(int(need))
-    lib.vae_launch_log_names(buf, need)
-    return buf.value.decode()
 
 
 FWD = [  # N, cin, cout, hw, stride, R, pad
@@ -42,7 +29,7 @@ FWD = [  # N, cin, cout, hw, stride, R, pad
 @pytest.mark.parametrize("shape", FWD)
 def test_bgemm_conv2d_fwd(shape):
     from vae_amd import _lib as L
-    log = _launched(lambda: run_fwd(False, *shape, L.X_NONE))
+    log = launched(lambda: run_fwd(False, *shape, L.X_NONE))
     assert "bgemm_kernel" in log, log
 
 
@@ -57,7 +44,7 @@ CONVT = [
 @pytest.mark.parametrize("give_wt_t", [False, True])
 def test_bgemm_convT2d_fwd(shape, give_wt_t):
     from vae_amd import _lib as L
-    log = _launched(lambda: run_fwd(True, *shape, L.X_NONE, give_wt_t=give_wt_t))
+    log = launched(lambda: run_fwd(True, *shape, L.X_NONE, give_wt_t=give_wt_t))
     assert "bgemm_kernel" in log, log
 
 
@@ -72,7 +59,7 @@ DGRAD = [  # N, cin, cout, hw (conv input), stride, R, pad
 def test_bgemm_conv2d_bwd_data(shape, epi):
     from vae_amd import _lib as L
     e = L.X_BN_ACT if epi == "bn_act" else L.X_ACT
-    log = _launched(lambda: run_dgrad(False, *shape, L.X_NONE, e))
+    log = launched(lambda: run_dgrad(False, *shape, L.X_NONE, e))
     assert "bgemm_kernel" in log, log
 
 
@@ -86,7 +73,7 @@ DGRAD_T = [  # N, cin, cout, hw (transposed conv input), stride, R, pad
 @pytest.mark.parametrize("shape", DGRAD_T)
 def test_bgemm_convT2d_bwd_data(shape):
     from vae_amd import _lib as L
-    log = _launched(lambda: run_dgrad(True, *shape, L.X_NONE, L.X_BN_ACT if shape[5] == 3 else L.X_ACT))
+    log = launched(lambda: run_dgrad(True, *shape, L.X_NONE, L.X_BN_ACT if shape[5] == 3 else L.X_ACT))
     assert "bgemm_kernel" in log, log
 
 
@@ -104,14 +91,14 @@ FWD_LAST = [
 @pytest.mark.parametrize("shape", FWD_LAST)
 def test_bgemm_conv2d_fwd_last_batch(shape):
     from vae_amd import _lib as L
-    log = _launched(lambda: run_fwd(False, *shape, L.X_NONE))
+    log = launched(lambda: run_fwd(False, *shape, L.X_NONE))
     print(log)
     assert "bgemm_kernel" in log, log
 
 
 def test_bgemm_convT2d_fwd_last_batch():
     from vae_amd import _lib as L
-    log = _launched(lambda: run_fwd(True, 29, 2048, 1024, 2, 2, 3, 1, L.X_NONE))       # M = 116 per phase
+    log = launched(lambda: run_fwd(True, 29, 2048, 1024, 2, 2, 3, 1, L.X_NONE))       # M = 116 per phase
     print(log)
     assert "bgemm_kernel" in log, log
 
@@ -120,14 +107,14 @@ def test_bgemm_convT2d_fwd_last_batch():
 def test_bgemm_conv2d_bwd_data_last_batch(epi):
     from vae_amd import _lib as L
     e = L.X_BN_ACT if epi == "bn_act" else L.X_ACT
-    log = _launched(lambda: run_dgrad(False, 29, 512, 1024, 8, 2, 3, 1, L.X_NONE, e))
+    log = launched(lambda: run_dgrad(False, 29, 512, 1024, 8, 2, 3, 1, L.X_NONE, e))
     print(log)
     assert "bgemm_kernel" in log, log
 
 
 def test_bgemm_convT2d_bwd_data_last_batch():
     from vae_amd import _lib as L
-    log = _launched(lambda: run_dgrad(True, 29, 1024, 512, 4, 2, 3, 1, L.X_NONE, L.X_BN_ACT))
+    log = launched(lambda: run_dgrad(True, 29, 1024, 512, 4, 2, 3, 1, L.X_NONE, L.X_BN_ACT))
     print(log)
     assert "bgemm_kernel" in log, log
 
@@ -182,7 +169,7 @@ def test_bwg_weight_gradient(shape):
     from test_gpu_cgemm import run_wgrad
     from vae_amd import _lib as L
     tr, *rest = shape
-    log = _launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
+    log = launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
     assert "bwg_kernel" in log, log
 
 
@@ -203,6 +190,6 @@ def test_bwg_weight_gradient_last_batch(shape):
     from test_gpu_cgemm import run_wgrad
     from vae_amd import _lib as L
     tr, *rest = shape
-    log = _launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
+    log = launched(lambda: run_wgrad(tr, *rest, L.X_NONE, L.X_NONE))
     print(log)
     assert "bwg_kernel" in log, log

@@ -9,7 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gpu_util import BNState, give_workspace, nhwc, rel, to_nchw, tol
+from gpu_util import BNState, give_workspace, launched, nhwc, rel, to_nchw, tol
 
 pytestmark = pytest.mark.gpu
 
@@ -230,9 +230,39 @@ def test_head_fwd_bwd(dtype, fused, C, N):
     in bf16 only (N = 9 at C = 128: 288 tiles, more than the persistent backward's 256 workgroups)."""
     if C != 32 and dtype != torch.bfloat16:
         pytest.skip("64/128-channel heads: bf16 MFMA kernels (fp32 plans take the conv-GEMM route)")
+    names = _head_case(dtype, fused, C, N, 64, mfma=dtype == torch.bfloat16)
+    if dtype == torch.bfloat16:
+        fwd = f"head_fwd_stream<{C}," if C == 128 else f"head_fwd_mfma<{C},"
+        bwd = "head_bwd_mfma<64, 2, 128>" if C == 128 else f"head_bwd_mfma<{C},"
+        assert fwd in names, names
+        assert bwd in names, names
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("C,fused", [(32, False), (64, False), (96, False), (32, True)])
+def test_head_valu_route(dtype, C, fused):
+    """The head on 32-wide images, which the MFMA kernels decline in either dtype: every entry point
+    takes its VALU route (8 image rows per tile, 4 tiles per image; C = 96 is the narrowest input
+    of the wide data-gradient kernel; fused: vae_head_bwd's fallback to the two unfused entry
+    points).  Reference and bars are test_head_fwd_bwd's."""
+    names = _head_case(dtype, fused, C, 2, 32, mfma=False)
+    for k in ("head_fwd_mfma", "head_fwd_stream", "head_bwd_mfma"):
+        assert k not in names, names
+    assert "head_fwd_kernel" in names and "head_bwd_filter_kernel" in names, names
+    data = [ln for ln in names.splitlines() if "head_bwd_data" in ln]
+    assert len(data) == 1, names
+    if C > 64:
+        assert "head_bwd_data_wide_kernel" in data[0], names
+    else:
+        assert "head_bwd_data_kernel" in data[0] and f"Li{C}E" in data[0], names   # (the mangled <T, C>)
+
+
+def _head_case(dtype, fused, C, N, H, mfma):
+    """One head forward + backward at [N, C, H, H] against autograd; returns the launch log.  mfma:
+    the call runs the bf16 MFMA kernels, whose reconstruction is also held against a reference
+    with their operand rounding."""
     L = _L()
     torch.manual_seed(6)
-    H = 64
     y_prev = torch.randn(N, C, H, H).requires_grad_()
     gam = 0.8 + 0.4 * torch.rand(C); bet = torch.rand(C) * 0.2 - 0.1
     gp = gam.clone().requires_grad_(); bp = bet.clone().requires_grad_()
@@ -259,26 +289,18 @@ def test_head_fwd_bwd(dtype, fused, C, N):
     a.dw = dw.data_ptr(); a.db = db.data_ptr()
     if fused:
         ws = give_workspace(a, "vae_head_bwd")
-    lib = L.load()
-    lib.vae_launch_log(1)
-    L.call("vae_head_fwd", ctypes.byref(a), _stream())
-    if fused:
-        L.call("vae_head_bwd", ctypes.byref(a), _stream())
-    else:
-        L.call("vae_head_bwd_data", ctypes.byref(a), _stream())
-        L.call("vae_head_bwd_filter", ctypes.byref(a), _stream())
-    lib.vae_launch_log(0)
+
+    def run():
+        L.call("vae_head_fwd", ctypes.byref(a), _stream())
+        if fused:
+            L.call("vae_head_bwd", ctypes.byref(a), _stream())
+        else:
+            L.call("vae_head_bwd_data", ctypes.byref(a), _stream())
+            L.call("vae_head_bwd_filter", ctypes.byref(a), _stream())
+    names = launched(run)
     torch.cuda.synchronize()
-    if dtype == torch.bfloat16:
-        need = lib.vae_launch_log_names(None, 0)
-        buf = ctypes.create_string_buffer(int(need))
-        lib.vae_launch_log_names(buf, need)
-        fwd = f"head_fwd_stream<{C}," if C == 128 else f"head_fwd_mfma<{C},"
-        bwd = "head_bwd_mfma<64, 2, 128>" if C == 128 else f"head_bwd_mfma<{C},"
-        assert fwd.encode() in buf.value, buf.value
-        assert bwd.encode() in buf.value, buf.value
     t = tol(dtype)
-    if dtype == torch.bfloat16:
+    if mfma:
         # the kernel's operands are bf16 (stored y, the activation it stages, the weights), so its
         # pre-tanh error grows as sqrt(9 C) of bf16 rounding (C = 128: up to 0.03 of max); against
         # the same rounding emulated only the fp32 summation order differs
@@ -304,6 +326,7 @@ def test_head_fwd_bwd(dtype, fused, C, N):
     # LeakyReLU branch (a factor 1/slope on an element that is ~0 anyway)
     d = dx.float().permute(0, 3, 1, 2).cpu()
     assert float((d - z.grad).norm() / z.grad.norm()) < t
+    return names
 
 
 def test_step_record_tracks_terms_per_image_and_extremes():

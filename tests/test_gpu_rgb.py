@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from gpu_util import launched
+
 pytestmark = pytest.mark.gpu
 
 SLOPE = 0.01
@@ -66,15 +68,9 @@ def test_rgb_out_fwd_recon_matches_torch(n):
     a.x_xf = L.Xform(kind=L.X_ACT, channels=128, slope=SLOPE)
     rc = L.ReconArgs(dtype=L.BF16, n=n, h=64, w=64, c=3, ld=8, grad_scale=1.0 / tgt.numel())
     rc.target, rc.recon, rc.sse, rc.dy = tgt_d.data_ptr(), recon.data_ptr(), sse.data_ptr(), dy.data_ptr()
-    lib = L.load()
-    lib.vae_launch_log(1)
-    L.call("vae_convT2d_fwd_recon", ctypes.byref(a), ctypes.byref(rc), L.stream_ptr())
-    lib.vae_launch_log(0)
+    names = launched(lambda: L.call("vae_convT2d_fwd_recon", ctypes.byref(a), ctypes.byref(rc), L.stream_ptr()))
     torch.cuda.synchronize()
-    need = lib.vae_launch_log_names(None, 0)
-    buf = ctypes.create_string_buffer(int(need))
-    lib.vae_launch_log_names(buf, need)
-    assert b"rgb_out_fwd_kernel" in buf.value, buf.value          # the dedicated kernel ran
+    assert "rgb_out_fwd_kernel" in names, names                   # the dedicated kernel ran
     np.testing.assert_allclose(recon.cpu().numpy(), r.detach().numpy(), rtol=0, atol=2e-5)
     np.testing.assert_allclose(sse.cpu().numpy(), ((r.detach() - tgt) ** 2).sum(dim=(1, 2, 3)).numpy(), rtol=1e-4)
     want = yr.grad.permute(0, 2, 3, 1)

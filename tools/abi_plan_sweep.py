@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the library's host planning answers over a sweep of the conv / convT / linear C ABI (CPU only).
+"""What the library's host planning answers over a sweep of the conv / convT / linear / head C ABI (CPU only).
 
     python3 tools/abi_plan_sweep.py [--pkg DIR] [--out FILE] [--no-short]
 
@@ -10,12 +10,14 @@ the native host side that must not change a plan is checked by running this on b
 points at the other one's pytorch-vae_amd, each with its own library) and comparing the files written
 with --out; no digest is stored here.
 
-Three parts:
+Four parts:
   base      the six conv entries over dtype x batch x geometry x channels x wt_t x deterministic
   extended  fewer shapes, crossed with the transform kind of the gathered operand and of the
             epilogue (BatchNorm pointers set) and one of: residual, split_k = 4, the NCHW fp32
             image, dw_inner, a fused BatchNorm finalisation, a tensor that is not 16-byte aligned
   linear    the three linear entries over dtype x rows x (n, k) x mulv x deterministic
+  head      the four decoder-head entries over dtype x batch x image size x channels x epilogue
+            kind x deterministic (both of the head's routes, and the widths it rejects)
 After each extended or linear query that reports a need, the entry itself is called with a workspace
 one word short: planning must reject it.  Such a call may get as far as a launch (a staged weight
 copy fits before the slab behind it is found short), and the tensors here are made-up addresses, so
@@ -39,6 +41,8 @@ NK = [(256, 2048), (2048, 512), (128, 128)]
 CONV_FNS = ["vae_conv2d_fwd", "vae_conv2d_bwd_data", "vae_conv2d_bwd_filter",
             "vae_convT2d_fwd", "vae_convT2d_bwd_data", "vae_convT2d_bwd_filter"]
 LINEAR_FNS = ["vae_linear_fwd", "vae_linear_bwd_data", "vae_linear_bwd_filter"]
+HEAD_FNS = ["vae_head_fwd", "vae_head_bwd_data", "vae_head_bwd_filter", "vae_head_bwd"]
+HEAD_C = [32, 64, 96, 128, 24, 40]       # (40: neither <= 32 nor a multiple of 32 — rejected)
 VARIANTS = ["plain", "residual", "split4", "residual+split4", "nchw", "dw_inner", "finalize", "odd_aux"]
 
 
@@ -101,6 +105,14 @@ def linear_args(L, dtype, m, nk, mulv, det, kind):
     return a
 
 
+def head_args(L, dtype, n, hw, c, kind, det):
+    a = L.HeadArgs(dtype=dtype, n=n, h=hw, w=hw, c=c, samples=1, deterministic=det)
+    for f in ("x", "wt", "bias", "target", "recon", "sse", "coef", "dx", "dx_dgamma", "dx_dbeta", "dw", "db"):
+        setattr(a, f, FAKE)
+    a.x_xf, a.dx_epi = _xform(L, L.X_BN_ACT, c), _xform(L, kind, c)
+    return a
+
+
 def query(L, fn, a):
     """(return code, workspace bytes, error text) of fn's workspace query for `a`."""
     lib = L.load()
@@ -152,6 +164,10 @@ def table(L, ck=CK, ck_ext=CK_EXT, nk=NK, short=True):
                                                               (L.X_NONE, L.X_BN_ACT)):
             line("linear", fn, f"dt={dtype} m={m} nk={s} mulv={mulv} det={det} xf={kind}",
                  linear_args(L, dtype, m, s, mulv, det, kind))
+    for fn in HEAD_FNS:
+        for dtype, n, hw, c, kind, det in itertools.product((L.BF16, L.F32), (2, 64), (64, 32), HEAD_C,
+                                                            (L.X_NONE, L.X_ACT, L.X_BN_ACT), (0, 1)):
+            line("head", fn, f"dt={dtype} n={n} hw={hw} c={c} e={kind} det={det}", head_args(L, dtype, n, hw, c, kind, det))
     return rows
 
 
