@@ -255,9 +255,9 @@ typedef struct vae_head_args {
 
 
 /* Loss kinds (vanilla_vae.py:124-146, beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211,
- * info_vae.py:128-148) */
+ * info_vae.py:128-148, dip_vae.py:125-164) */
 enum vae_loss_kind { VAE_LOSS_VANILLA = 0, VAE_LOSS_BETA_H = 1, VAE_LOSS_BETA_B = 2, VAE_LOSS_IWAE = 3,
-                     VAE_LOSS_VQ = 4, VAE_LOSS_INFO = 5 };
+                     VAE_LOSS_VQ = 4, VAE_LOSS_INFO = 5, VAE_LOSS_DIP = 6 };
 
 typedef struct vae_elbo_args {
   int32_t kind;            /* vae_loss_kind */
@@ -289,7 +289,48 @@ typedef struct vae_elbo_args {
   int32_t mmd_tiles;
   const double* mmd_partials;
   float* mmd_out;          /* [1] */
+  /* VAE_LOSS_DIP (DIP-VAE, dip_vae.py:125-164; one sample): both terms are SUMS, as the reference's
+   *   F.mse_loss(reduction='sum') and torch.sum over the batch are:
+   *   loss = recon + kld_weight*kld + dip, recon = Σ_i sse_i, kld = Σ_b kld_b;
+   *   dip = sum over t < mmd_tiles, in ascending order, of the vae_dip partials (doubles, 2 per tile,
+   *   the first of each pair) — the batch-coupled term takes the three fields above, so the struct
+   *   keeps its size: mmd_tiles = the tile count of vae_dip_workspace_size, mmd_partials = the
+   *   vae_dip workspace, mmd_out[0] = dip (the dict's DIP_Loss);
+   *   head_coef = 2 (dL/dsse_i = 1: no 1/(B*img_elems)), kl_coef = kld_weight (no 1/B);
+   *   out = {loss, Reconstruction_Loss, -kld (as the reference reports it), kld};
+   *   per_img stays the per-image mean MSE (experiment.py:60-62). */
 } vae_elbo_args;
+
+/* DIP-VAE's covariance penalty on the batch's latent means and its gradient ("DIP loss II",
+ * DIPVAE.loss_function, dip_vae.py:146-158), from mulv = [mu | log_var]:
+ *   c = mu - mean_d(mu): centred over the LATENT axis, per row (the reference's mean(dim=1));
+ *   Cov = c^T c [latent][latent], summed over the batch with no 1/B;
+ *   s = mean_{i < min(batch,latent)} exp(2*log_var[i][i]): torch.diagonal(dim1=0) of the
+ *     [batch][latent] matrix, a scalar, added to EVERY entry: cov_z = Cov + s;
+ *   dip = lambda_offdiag * Σ_{j!=k} cov_z[j][k]^2 + lambda_diag * Σ_j (cov_z[j][j] - 1)^2.
+ *   With G = d dip/d cov_z (2*lambda_offdiag*cov_z off the diagonal, 2*lambda_diag*(cov_z - 1) on it)
+ *   and X = 2 c G:  d dip/d mu = X - mean_d(X);  d dip/d log_var[i][i] = (Σ G) * 2 exp(2 log_var[i][i])
+ *   / min(batch,latent) for i < min(batch,latent), zero for every other element.
+ *   dmulv_dip [batch][2*latent] = grad_scale * d dip/d[mu | log_var] (every element written); with
+ *   dmulv set the same values are added to it (the convention of vae_mmd_args.dmulv).
+ * Two launches, no atomics (repeated calls are bit-identical): a workgroup per strip of 16 columns of
+ * Cov streams the centred rows through LDS twice — Cov strip = c^T c (k = batch), then X strip =
+ * 2 c G (k = latent), both on v_mfma_f32_16x16x4_f32 — and leaves {dip share, Σ G share} as doubles
+ * [tiles][2] at the head of the workspace, followed by its share of every row sum of X as floats
+ * [tiles][batch]; a second launch (a workgroup per row) adds those in tile order, subtracts the row
+ * mean and writes the gradient.  vae_elbo_fwd (VAE_LOSS_DIP) adds the dip shares in tile order.
+ * Shapes: 1 <= batch <= 1024, latent % 32 == 0, latent <= 256 (VAE_E_BADSHAPE otherwise). */
+typedef struct vae_dip_args {
+  int32_t batch, latent;
+  float lambda_diag, lambda_offdiag;
+  float grad_scale;
+  int32_t reserved;
+  const float* mulv;       /* [batch][2*latent], 8-byte aligned */
+  float* dmulv_dip;        /* [batch][2*latent] out */
+  float* dmulv;            /* [batch][2*latent] accumulated, or NULL */
+  void* workspace;         /* vae_dip_workspace_size bytes, 8-byte aligned */
+  int64_t workspace_bytes;
+} vae_dip_args;
 
 /* Maximum mean discrepancy between the batch of latents and a prior sample, and its gradient
  * (InfoVAE.compute_mmd, info_vae.py:150-229; the same term WAE-MMD uses).
@@ -460,6 +501,11 @@ int vae_mmd_fwd(const vae_mmd_args* a, void* stream);
 int vae_mmd_workspace_size(const vae_mmd_args* a, size_t* bytes, int32_t* tiles);
 int vae_mmd_reseed(int32_t batch, int32_t latent, const float* dz, const float* scale, const float* mulv,
                    const float* eps, float* dmulv, void* stream);
+/* --- DIP-VAE covariance penalty of the latent means + its gradient (dip_vae.py:146-158), see
+ *     vae_dip_args.  vae_dip_workspace_size: bytes of the workspace (host only; *tiles, if set, gets
+ *     the tile count vae_elbo_args.mmd_tiles takes for VAE_LOSS_DIP). */
+int vae_dip_fwd(const vae_dip_args* a, void* stream);
+int vae_dip_workspace_size(const vae_dip_args* a, size_t* bytes, int32_t* tiles);
 /* --- Adam (experiment.py:308-311; torch.optim.Adam semantics), flat fp32 buffers.
  *     step/lr are device scalars so the call can be replayed from a graph.  When
  *     p_lowp != NULL the updated parameters are also written as bf16 (weight copies). --- */

@@ -19,7 +19,11 @@ using namespace vae;
 
 extern "C" int vae_elbo_fwd(const vae_elbo_args* a, void* stream) {
   if (!a || !a->sse || !a->out || !a->per_img) return fail(VAE_E_BADARG, "elbo_fwd: args");
-  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_INFO) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_DIP) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind == VAE_LOSS_DIP) {
+    if (!a->mmd_partials || !a->mmd_out || a->mmd_tiles <= 0) return fail(VAE_E_BADARG, "elbo_fwd: dip partials / dip out (mmd_partials, mmd_out, mmd_tiles)");
+    if (a->samples > 1) return fail(VAE_E_BADSHAPE, "elbo_fwd: DIP-VAE takes one sample");
+  }
   if (a->kind == VAE_LOSS_INFO) {
     if (!a->mmd_partials || !a->mmd_out || a->mmd_tiles <= 0) return fail(VAE_E_BADARG, "elbo_fwd: mmd partials / mmd_out");
     if (a->batch < 2 || a->samples > 1) return fail(VAE_E_BADSHAPE, "elbo_fwd: InfoVAE needs batch >= 2, one sample");

@@ -1,5 +1,5 @@
 // ELBO of the VAE family on one workgroup (vaehip.h vae_elbo_fwd; vanilla_vae.py:124-146,
-// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211, info_vae.py:128-148).
+// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211, info_vae.py:128-148, dip_vae.py:125-164).
 #pragma once
 #include "vae_common.hpp"
 
@@ -47,6 +47,20 @@ __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_ro
     const float recon = sse_tot / ((float)B * (float)a.img_elems);
     const float vq = (1.f + a.vq_beta) * (*a.vq_sse) / a.vq_elems;
     if (threadIdx.x == 0) { a.out[0] = recon + vq; a.out[1] = recon; a.out[2] = vq; a.out[3] = 0.f; }
+    return;
+  }
+  if (a.kind == VAE_LOSS_DIP) {
+    // dip_vae.py:141-164: recon and kld are sums; the DIP term is the vae_dip partials (the first
+    // double of each tile's pair) added in tile order by every thread
+    double dip_d = 0.0;
+    for (int t = 0; t < a.mmd_tiles; ++t) dip_d += a.mmd_partials[2 * t];
+    const float dip = (float)dip_d;
+    const float kld_sum = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    for (int i = threadIdx.x; i < B; i += 256) { a.head_coef[i] = 2.f; a.kl_coef[i] = a.kld_weight; }
+    if (threadIdx.x == 0) {
+      a.out[0] = sse_tot + a.kld_weight * kld_sum + dip; a.out[1] = sse_tot; a.out[2] = -kld_sum; a.out[3] = kld_sum;
+      a.mmd_out[0] = dip;
+    }
     return;
   }
   if (a.kind != VAE_LOSS_IWAE) {

@@ -23,7 +23,7 @@ ABI_VERSION = 26
 
 F32, BF16 = 0, 1
 X_NONE, X_ACT, X_BN_ACT, X_BN_DY = 0, 1, 2, 3
-LOSS_VANILLA, LOSS_BETA_H, LOSS_BETA_B, LOSS_IWAE, LOSS_VQ, LOSS_INFO = 0, 1, 2, 3, 4, 5
+LOSS_VANILLA, LOSS_BETA_H, LOSS_BETA_B, LOSS_IWAE, LOSS_VQ, LOSS_INFO, LOSS_DIP = 0, 1, 2, 3, 4, 5, 6
 MMD_IMQ, MMD_RBF = 0, 1                                          # vaehip.h enum vae_mmd_kind
 
 
@@ -99,6 +99,13 @@ class MmdArgs(ctypes.Structure):
                 ("grad_scale", c_float), ("prior_gen", c_int32), ("mulv", c_void_p), ("eps", c_void_p),
                 ("prior", c_void_p), ("dz", c_void_p), ("dmulv", c_void_p), ("workspace", c_void_p),
                 ("workspace_bytes", c_int64), ("prior_step", c_void_p), ("prior_seed", ctypes.c_uint64)]
+
+
+class DipArgs(ctypes.Structure):
+    """vaehip.h vae_dip_args (DIP-VAE's covariance penalty of the latent means + its gradient)."""
+    _fields_ = [("batch", c_int32), ("latent", c_int32), ("lambda_diag", c_float), ("lambda_offdiag", c_float),
+                ("grad_scale", c_float), ("reserved", c_int32), ("mulv", c_void_p), ("dmulv_dip", c_void_p),
+                ("dmulv", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_int64)]
 
 
 SLAB_MAX = 32                      # vaehip.h VAE_SLAB_MAX
@@ -219,6 +226,8 @@ _SIGS = {
     "vae_mmd_fwd": [POINTER(MmdArgs), c_void_p],
     "vae_mmd_workspace_size": [POINTER(MmdArgs), POINTER(ctypes.c_size_t), POINTER(c_int32)],
     "vae_mmd_reseed": [c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "vae_dip_fwd": [POINTER(DipArgs), c_void_p],
+    "vae_dip_workspace_size": [POINTER(DipArgs), POINTER(ctypes.c_size_t), POINTER(c_int32)],
     "vae_vq_fwd": [POINTER(VqArgs), c_void_p],
     "vae_vq_bwd": [POINTER(VqArgs), c_void_p],
     "vae_recon_fwd": [POINTER(ReconArgs), c_void_p],
@@ -404,6 +413,13 @@ def mmd_workspace(a: "MmdArgs"):
     """(bytes of partials, tile count) of a vae_mmd_fwd call (vae_mmd_workspace_size; no device)."""
     out, tiles = ctypes.c_size_t(0), c_int32(0)
     call("vae_mmd_workspace_size", ctypes.byref(a), ctypes.byref(out), ctypes.byref(tiles))
+    return int(out.value), int(tiles.value)
+
+
+def dip_workspace(a: "DipArgs"):
+    """(bytes of workspace, tile count) of a vae_dip_fwd call (vae_dip_workspace_size; no device)."""
+    out, tiles = ctypes.c_size_t(0), c_int32(0)
+    call("vae_dip_workspace_size", ctypes.byref(a), ctypes.byref(out), ctypes.byref(tiles))
     return int(out.value), int(tiles.value)
 
 

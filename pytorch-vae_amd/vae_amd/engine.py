@@ -245,10 +245,11 @@ class TrainStep:
             p._run(p.fwd_calls[skip:], st)
             if self.comm is not None and not p.elbo_in_head:
                 p.metrics.copy_(p.out)
-                if p.loss_kind == L.LOSS_INFO:
-                    # the fourth logged term of an InfoVAE step (each rank's MMD is over its own
-                    # shard, as under the reference's DDP; the all-reduce makes it the rank mean)
-                    p.metrics[3:4].copy_(p.mmd)
+                if p.extra_term is not None:
+                    # the fourth logged term of an InfoVAE / DIP-VAE step (each rank's MMD or DIP_Loss
+                    # is over its own shard, as under the reference's DDP; the all-reduce makes it the
+                    # rank mean)
+                    p.metrics[3:4].copy_(p.extra_term[1])
         lo = 0 if k == 0 else self.buckets[k - 1][0]
         if self.deferred:
             L.call("vae_deferred_reset")
@@ -438,9 +439,17 @@ class TrainStep:
         than one (what the reference logs, experiment.py:55), else this rank's."""
         return (self.plan.metrics if self.comm is not None else self.plan.out)[:3].tolist()
 
+    def extra_term(self):
+        """(name, value) of the fourth entry of the last step's loss dict — InfoVAE's 'MMD'
+        (info_vae.py:148), DIP-VAE's 'DIP_Loss' (dip_vae.py:164) — the mean over ranks with more than
+        one; None for a loss without one."""
+        term = self.plan.extra_term
+        if term is None:
+            return None
+        return term[0], float(self.plan.metrics[3] if self.comm is not None else term[1])
+
     def mmd_term(self) -> float:
-        """InfoVAE: the 'MMD' entry of the last step's loss dict (info_vae.py:148), the mean over ranks
-        with more than one."""
+        """InfoVAE: the 'MMD' entry of the last step's loss dict (extra_term)."""
         if self.plan.loss_kind != L.LOSS_INFO:
             raise ValueError("this step's loss has no MMD term")
-        return float(self.plan.metrics[3] if self.comm is not None else self.plan.mmd)
+        return self.extra_term()[1]

@@ -295,11 +295,11 @@ class GraphedSteps:
         dev = imgs.device
         if self._ext is None:
             ie = plan.x[0].numel()
-            info = plan.prior is not None                                       # InfoVAE: a fourth term
-            self._terms_buf = torch.zeros(4 if info else 3, device=dev)
+            extra = plan.extra_term                                   # InfoVAE / DIP-VAE: a fourth term
+            self._terms_buf = torch.zeros(4 if extra is not None else 3, device=dev)
             self._terms = {k: self._terms_buf[i] for i, k in enumerate(plan.loss_names)}
-            if info:
-                self._terms['MMD'] = self._terms_buf[3]
+            if extra is not None:
+                self._terms[extra[0]] = self._terms_buf[3]
             if step.zero_eps:                                                   # Autoencoder
                 z = torch.zeros((), device=dev)
                 self._terms.update(KLD=z, feature_loss=z)
@@ -320,8 +320,8 @@ class GraphedSteps:
         a.hi_img, a.lo_img = e['img'][0].data_ptr(), e['img'][1].data_ptr()
         a.hi_recon, a.lo_recon = e['recon'][0].data_ptr(), e['recon'][1].data_ptr()
         L.call("vae_step_record", ctypes.byref(a), L.stream_ptr())
-        if 'MMD' in self._terms:           # info_vae.py:148 (with more ranks: the rank mean, metrics[3])
-            self._terms_buf[3:4].copy_(plan.metrics[3:4] if step.world > 1 else plan.mmd)
+        if plan.extra_term is not None:    # info_vae.py:148, dip_vae.py:164 (with more ranks: the rank mean, metrics[3])
+            self._terms_buf[3:4].copy_(plan.metrics[3:4] if step.world > 1 else plan.extra_term[1])
         self._per.append((self._per_off, B))
         self._per_off += B
 

@@ -7,6 +7,7 @@ Mirrors the reference interface (paths relative to the reference root):
   BetaVAE                 models/beta_vae.py:8-179  (loss_type 'H' / 'B', per-instance num_iter)
   IWAE                    models/iwae.py:8-188      (num_samples; row-major b*S+s latent order)
   InfoVAE                 models/info_vae.py:8-256  (MMD term on vae_mmd_fwd; imq / rbf kernels)
+  DIPVAE                  models/dip_vae.py:8-191   (covariance penalty of the means on vae_dip_fwd)
   VQVAE                   models/vq_vae.py:73-219   (VectorQuantizer, residual stacks; vae_amd/vq.py)
   vae_models registry     models/__init__.py:35-56
 
@@ -159,10 +160,12 @@ class _HipELBO(torch.autograd.Function):
         # InfoVAE: a third seed, dmmd/dz (vae_mmd_fwd at run_elbo), applied scaled in the backward;
         # the loss dict's MMD entry is a fourth output
         ctx.mmd_seed = (plan.dz_mmd.clone(), plan.mmd_coef) if loss_kw["loss"] == "info" else None
-        if ctx.mmd_seed is not None:
-            mmd = plan.mmd[0].clone()
-            ctx.mark_non_differentiable(rl, kld, mmd)
-            return loss, rl, kld, mmd
+        # DIP-VAE: likewise d dip/d[mu | log_var] (vae_dip_fwd at run_elbo) and the DIP_Loss entry
+        ctx.dip_seed = plan.dmulv_dip.clone() if loss_kw["loss"] == "dip" else None
+        if ctx.mmd_seed is not None or ctx.dip_seed is not None:
+            fourth = plan.extra_term[1][0].clone()
+            ctx.mark_non_differentiable(rl, kld, fourth)
+            return loss, rl, kld, fourth
         ctx.mark_non_differentiable(rl, kld)
         return loss, rl, kld
 
@@ -179,6 +182,8 @@ class _HipELBO(torch.autograd.Function):
         if ctx.mmd_seed is not None:
             plan.dz_mmd.copy_(ctx.mmd_seed[0])
             plan.seed_mmd(g_loss, ctx.mmd_seed[1], L.stream_ptr())
+        if ctx.dip_seed is not None:
+            plan.seed_dip(g_loss, ctx.dip_seed)
         plan.seed_fused(True)
         try:
             plan.backward(L.stream_ptr())
@@ -567,6 +572,55 @@ class InfoVAE(_HipVAE):
                 - 2 * self.compute_kernel(prior_z, z).mean())
 
 
+class DIPVAE(_HipVAE):
+    """models/dip_vae.py:8-191 on libvaehip: the VanillaVAE network with the loss
+    recon + M_N * kld + dip, recon and kld SUMS over the batch, dip the penalty on the covariance of the
+    batch's latent means (vae_dip_fwd; the reference's quirks kept)."""
+
+    def __init__(self, in_channels: int, latent_dim: int, hidden_dims: List = None, lambda_diag: float = 10.,
+                 lambda_offdiag: float = 5., **kwargs) -> None:
+        super().__init__(in_channels, latent_dim, hidden_dims, **kwargs)
+        self.lambda_diag = lambda_diag
+        self.lambda_offdiag = lambda_offdiag
+
+    def _loss_config(self) -> dict:
+        return dict(loss="dip", lambda_diag=float(self.lambda_diag), lambda_offdiag=float(self.lambda_offdiag))
+
+    def _dropin_config(self) -> dict:
+        return self._loss_config()
+
+    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
+        """dip_vae.py:120-123: [recons, input, mu, log_var]."""
+        recon, mu, log_var, _ = self._run(input, kwargs.get("eps"))
+        out = [recon, input, mu, log_var]
+        self._remember(out)
+        return out
+
+    def loss_function(self, *args, **kwargs) -> dict:
+        """dip_vae.py:125-164."""
+        kld_weight = kwargs['M_N']
+        last = self._last
+        # (the drop-in plan holds the lambdas it was built with: a model whose lambdas were changed
+        # afterwards takes the torch formula)
+        if last is not None and (last[0].lambda_diag, last[0].lambda_offdiag) == (float(self.lambda_diag),
+                                                                                 float(self.lambda_offdiag)):
+            g = self._gpu_loss(args, "dip", kld_weight=kld_weight)
+            if g is not None:
+                return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2], 'DIP_Loss': g[3]}
+        recons, input, mu, log_var = args[0], args[1], args[2], args[3]
+        recons_loss = F.mse_loss(recons, input, reduction='sum')
+        kld_loss = torch.sum(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
+        centered_mu = mu - mu.mean(dim=1, keepdim=True)
+        cov_mu = centered_mu.t().matmul(centered_mu).squeeze()
+        cov_z = cov_mu + torch.mean(torch.diagonal((2. * log_var).exp(), dim1=0), dim=0)
+        cov_diag = torch.diag(cov_z)
+        cov_offdiag = cov_z - torch.diag(cov_diag)
+        dip_loss = (self.lambda_offdiag * torch.sum(cov_offdiag ** 2)
+                    + self.lambda_diag * torch.sum((cov_diag - 1) ** 2))
+        loss = recons_loss + kld_weight * kld_loss + dip_loss
+        return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'KLD': -kld_loss, 'DIP_Loss': dip_loss}
+
+
 class MSSIM(nn.Module):
     """models/mssim_vae.py:182-282: the differentiable MS-SSIM loss 1 - Π cs_l^w_l · ssim_L^w_L over five
     levels (11x11 window, avg-pool 2x2 between levels, size_average, dynamic range 1, normalised
@@ -906,7 +960,7 @@ class VQVAE(BaseVAE):
 
 # models/__init__.py:35-56: the families on the MI355X path; the others raise on use.
 _ON_PATH = {'VanillaVAE': VanillaVAE, 'BetaVAE': BetaVAE, 'IWAE': IWAE, 'VQVAE': VQVAE, 'Autoencoder': Autoencoder,
-            'InfoVAE': InfoVAE}
+            'InfoVAE': InfoVAE, 'DIPVAE': DIPVAE}
 _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 'DIPVAE', 'BetaVAE', 'InfoVAE',
                     'WAE_MMD', 'VampVAE', 'GammaVAE', 'MSSIMVAE', 'JointVAE', 'BetaTCVAE', 'FactorVAE',
                     'LogCoshVAE', 'VanillaVAE', 'ConditionalVAE', 'CategoricalVAE', 'Autoencoder']
@@ -915,7 +969,8 @@ _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 
 def _not_on_path(name):
     def ctor(*args, **kwargs):
         raise NotImplementedError(f"{name} is not on the MI355X training path of this build "
-                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE are; DESIGN.md §7)")
+                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE, DIPVAE are; "
+                                  f"DESIGN.md §7)")
     return ctor
 
 

@@ -71,9 +71,11 @@ class VAENet(NetBase):
 class StepPlan(PlanBase):
     """All buffers and prebuilt launches of one training step for a fixed batch shape.
 
-    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae' | 'info';  samples: IWAE S (decoder batch B*S).
+    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae' | 'info' | 'dip';  samples: IWAE S (decoder batch B*S).
     'info' (InfoVAE, models/info_vae.py:128-229) takes alpha, beta, reg_weight, kernel_type and
     latent_var; its MMD term runs on vae_mmd_fwd right after the reparameterization.
+    'dip' (DIP-VAE, models/dip_vae.py:125-164) takes lambda_diag and lambda_offdiag; its covariance
+    penalty runs on vae_dip_fwd as soon as mu | log_var are final.
     grads land in `self.grads` (same layout as net.params); `zero` (grads, BN sums, SSE,
     d[mu|logvar]) is cleared by `vae_step_begin` at the start of every step."""
 
@@ -85,7 +87,8 @@ class StepPlan(PlanBase):
                  deterministic: Optional[bool] = None, latent_kernels: bool = True, head_kernels: bool = True,
                  pad_rgb: bool = True, materialise: bool = True, mat_min_flops: float = MAT_MIN_FLOPS,
                  batch_wgrads: bool = True, alpha: float = -0.5, reg_weight: float = 100.0,
-                 kernel_type: str = "imq", latent_var: float = 2.0):
+                 kernel_type: str = "imq", latent_var: float = 2.0, lambda_diag: float = 10.0,
+                 lambda_offdiag: float = 5.0):
         # Route options (explicit arguments; every non-default route has a GPU test,
         # tests/test_gpu_routes.py): latent_kernels / head_kernels / pad_rgb / materialise /
         # batch_wgrads = False keep the generic per-op calls in place of the dedicated bottleneck
@@ -124,10 +127,11 @@ class StepPlan(PlanBase):
         self.kld_weight, self.beta, self.gamma = kld_weight, beta, gamma
         if kernel_type not in MMD_KINDS:
             raise ValueError('Undefined kernel type.')                   # info_vae.py:173
-        if loss == "info" and fused_loss and not training:
-            # an eval plan has no MMD call (nothing to seed), so the fused VAE_LOSS_INFO ELBO would
-            # find no partials: the loss of an eval forward is the caller's (models.InfoVAE)
-            raise ValueError("StepPlan(loss='info', training=False) has no fused loss: pass fused_loss=False")
+        if loss in ("info", "dip") and fused_loss and not training:
+            # an eval plan has no MMD / DIP call (nothing to seed), so the fused ELBO would find no
+            # partials: the loss of an eval forward is the caller's (models.InfoVAE, models.DIPVAE)
+            raise ValueError(f"StepPlan(loss='{loss}', training=False) has no fused loss: pass fused_loss=False")
+        self.lambda_diag, self.lambda_offdiag = lambda_diag, lambda_offdiag
         self.alpha, self.reg_weight, self.kernel_type, self.latent_var = alpha, reg_weight, kernel_type, latent_var
         self.c_max, self.c_stop = max_capacity, capacity_max_iter
         dev, T = net.device, net.dtype
@@ -188,6 +192,12 @@ class StepPlan(PlanBase):
             self.dz_mmd = torch.zeros(B, D, **f32)
             self.mmd = torch.zeros(1, **f32)
             self._mmd_scale = torch.zeros(1, **f32)                       # drop-in backward: dL/dloss * mmd_coef
+        # DIP-VAE's covariance penalty (vae_dip_fwd): its gradient d dip/d[mu | log_var], the dip value
+        # (vae_elbo_fwd writes it) and the workspace of tile partials
+        self.dmulv_dip = self.dip = self.dip_ws = None
+        if self.loss_kind == L.LOSS_DIP and training:
+            self.dmulv_dip = torch.zeros(B, 2 * D, **f32)
+            self.dip = torch.zeros(1, **f32)
         # backward buffers (gradients w.r.t. pre-activation of each stored tensor)
         self.g_enc = [torch.empty_like(t) for t in self.enc]
         self.g_h0 = torch.empty_like(self.h0)
@@ -502,6 +512,7 @@ class StepPlan(PlanBase):
             self.n_encode = self.n_decode0 = len(F)     # (decode() of a fused plan starts at the reparameterization)
             F.append(("vae_latent_dec_fwd", F[-1][1]))
             self._add_mmd(F)                   # (behind the kernel that draws / reads this step's eps)
+            self._add_dip(F)
             return
         a = L.LinearArgs(dtype=T, m=B, n=2 * D, k=4 * C5)
         a.x, a.x_xf = last.data_ptr(), self.bn_xf(pre, L.X_BN_ACT, _cnt(last), running=True)
@@ -511,6 +522,7 @@ class StepPlan(PlanBase):
         self.n_encode = len(F)             # calls of encode(): encoder + fc_mu|fc_var
         F.append(("vae_reparam_fwd", (T, BS, self.S, D, self.mulv.data_ptr(), self.eps.data_ptr(), self.z.data_ptr())))
         self._add_mmd(F)
+        self._add_dip(F)
         self.n_decode0 = len(F)            # decode(): decoder_input .. head
         a = L.LinearArgs(dtype=T, m=BS, n=4 * r0, k=D)
         a.x, a.y = self.z.data_ptr(), self.h0.data_ptr()
@@ -571,6 +583,8 @@ class StepPlan(PlanBase):
         if self.mmd_ws is not None:
             self._info_coefs(e, self.beta, self.alpha, self.reg_weight)
             e.mmd_tiles, e.mmd_partials, e.mmd_out = self._mmd_tiles, self.mmd_ws.data_ptr(), self.mmd.data_ptr()
+        if self.dip_ws is not None:        # (VAE_LOSS_DIP reads its partials through the same three fields)
+            e.mmd_tiles, e.mmd_partials, e.mmd_out = self._dip_tiles, self.dip_ws.data_ptr(), self.dip.data_ptr()
         self.n_decode1, self.elbo_args = len(F), e
         # elbo_in_head: the loss evaluated by the head backward (vaehip.h vae_head_args.elbo: one
         # extra workgroup of its filter-partial reduction, the seed coefficient a constant) instead
@@ -733,6 +747,26 @@ class StepPlan(PlanBase):
             a.grad_scale = 1.0
             self._keep.append(a)
 
+    def _add_dip(self, F):
+        """DIP-VAE: the covariance penalty of this step's latent means and its gradient (vae_dip_fwd),
+        as soon as mu | log_var are final; it needs neither eps nor z.  In a fused-loss plan the call is
+        part of the forward and adds d dip/d[mu | log_var] into dmulv itself (the term's weight in the
+        loss is 1); in a drop-in plan it runs at loss_function time (run_elbo) and the backward applies
+        the stored gradient scaled by dL/dloss (seed_dip)."""
+        if self.loss_kind != L.LOSS_DIP or not self.training:
+            return
+        a = self._dip = L.DipArgs(batch=self.B, latent=self.net.latent_dim, lambda_diag=self.lambda_diag,
+                                  lambda_offdiag=self.lambda_offdiag, grad_scale=1.0)
+        a.mulv, a.dmulv_dip = self.mulv.data_ptr(), self.dmulv_dip.data_ptr()
+        nbytes, self._dip_tiles = L.dip_workspace(a)
+        self.dip_ws = torch.zeros(nbytes // 8 + 1, dtype=torch.float64, device=self.net.device)
+        a.workspace, a.workspace_bytes = self.dip_ws.data_ptr(), self.dip_ws.numel() * 8
+        if self.fused_loss:
+            a.dmulv = self.dmulv.data_ptr()
+            self._add(F, "vae_dip_fwd", a)
+        else:
+            self._keep.append(a)
+
     def _add_recon_loss(self, F):
         """The recon_loss call closing the forward (vae_recon_loss): loss terms into `out`, per-image
         MSE from the head's SSE, and dL/drecon into grad_recon for the backward."""
@@ -767,7 +801,9 @@ class StepPlan(PlanBase):
         rc = L.ReconArgs(dtype=T, n=BS, h=img, w=img, c=3, ld=8)
         rc.y, rc.target, rc.recon, rc.sse = self.y8.data_ptr(), self.x.data_ptr(), self.recon.data_ptr(), self.sse.data_ptr()
         if self.fused_loss and self.training and self.recon_loss is None:
-            rc.dy, rc.grad_scale = self.g8.data_ptr(), 1.0 / (self.B * 3 * img * img)
+            # (DIP-VAE's reconstruction term is the sum, dip_vae.py:141: no 1/(B*3*H*W))
+            rc.dy = self.g8.data_ptr()
+            rc.grad_scale = 1.0 if self.loss_kind == L.LOSS_DIP else 1.0 / (self.B * 3 * img * img)
         self._add(F, "vae_recon_fwd", rc)
 
     def _wide_head_bwd(self, Bw):
@@ -846,7 +882,19 @@ class StepPlan(PlanBase):
         d = super().loss_dict()
         if self.loss_kind == L.LOSS_INFO:       # info_vae.py:148: MMD before KLD
             d["MMD"], d["KLD"] = float(self.mmd), d.pop("KLD")
+        elif self.loss_kind == L.LOSS_DIP:      # dip_vae.py:161-164: DIP_Loss last
+            d["DIP_Loss"] = float(self.dip)
         return d
+
+    @property
+    def extra_term(self):
+        """(name, one-element tensor) of the loss dict's fourth entry, for the losses with a
+        batch-coupled latent term (InfoVAE's MMD, DIP-VAE's DIP_Loss); None otherwise."""
+        if self.mmd is not None:
+            return "MMD", self.mmd
+        if self.dip is not None:
+            return "DIP_Loss", self.dip
+        return None
 
     # ------------------------------------------------------------------ drop-in ELBO
     # A drop-in plan (fused_loss=False) can still take its loss on the GPU: the BaseVAE
@@ -854,7 +902,7 @@ class StepPlan(PlanBase):
     # and seeds the backward from the kernel's coefficients (seed_fused) instead of autograd's
     # dL/drecon and dL/d[mu|log_var].
     LOSS_KINDS = {"vanilla": L.LOSS_VANILLA, "betaH": L.LOSS_BETA_H, "betaB": L.LOSS_BETA_B,
-                  "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO}
+                  "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO, "dip": L.LOSS_DIP}
 
     def run_elbo(self, stream, loss: str, kld_weight: float, beta: float = 4.0, gamma: float = 1000.0,
                  c_max: float = 25.0, c_stop_iter: float = 1e5, num_iter: Optional[int] = None,
@@ -877,7 +925,19 @@ class StepPlan(PlanBase):
                 self.prior.copy_(prior.detach().reshape(self.prior.shape))
             self.mmd_coef = self._info_coefs(e, beta, alpha, reg_weight)
             L.call("vae_mmd_fwd", self._mmd, stream)
+        if e.kind == L.LOSS_DIP:
+            # the penalty of this forward's means: its unscaled gradient into dmulv_dip, the partials the
+            # loss adds into the workspace (the lambdas are the plan's)
+            if self.dip_ws is None or self.fused_loss:
+                raise ValueError("run_elbo('dip') needs a drop-in plan built with loss='dip'")
+            L.call("vae_dip_fwd", self._dip, stream)
         L.call("vae_elbo_fwd", e, stream)
+
+    def seed_dip(self, g_loss: torch.Tensor, seed: torch.Tensor):
+        """Drop-in backward of the DIP term: dmulv += dL/dloss * seed, the d dip/d[mu | log_var] that
+        vae_dip_fwd stored at run_elbo, next to the two seeds seed_fused switches on.  dmulv is zero
+        here (the step head or reset_backward) and the backward accumulates onto it."""
+        self.dmulv.view(seed.shape).addcmul_(seed, g_loss.reshape(1, 1).to(seed))
 
     def seed_mmd(self, g_loss: torch.Tensor, mmd_coef: float, stream):
         """Drop-in backward of the MMD term: dmulv += reparameterization backward of

@@ -137,6 +137,7 @@ class PlanBase:
     wg_overlap = False      # the decoder's weight gradients as a side-stream batch (StepPlan)
     elbo_in_head = False    # the loss is evaluated by the head backward, not by the forward
     prior = None            # InfoVAE's prior sample (an input of the step)
+    extra_term = None       # (name, one-element tensor): a fourth loss-dict entry (MMD, DIP_Loss)
     backward_done = False   # drop-in models: the backward of the last forward has run (models.py)
     deferred = False        # defer_reductions() has run: the backward leaves unreduced partials
     loss_names = ("loss", "Reconstruction_Loss", "KLD")     # the first three entries of `out`
