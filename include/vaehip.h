@@ -255,9 +255,9 @@ typedef struct vae_head_args {
 
 
 /* Loss kinds (vanilla_vae.py:124-146, beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211,
- * info_vae.py:128-148, dip_vae.py:125-164) */
+ * info_vae.py:128-148, dip_vae.py:125-164, miwae.py:132-164) */
 enum vae_loss_kind { VAE_LOSS_VANILLA = 0, VAE_LOSS_BETA_H = 1, VAE_LOSS_BETA_B = 2, VAE_LOSS_IWAE = 3,
-                     VAE_LOSS_VQ = 4, VAE_LOSS_INFO = 5, VAE_LOSS_DIP = 6 };
+                     VAE_LOSS_VQ = 4, VAE_LOSS_INFO = 5, VAE_LOSS_DIP = 6, VAE_LOSS_MIWAE = 7 };
 
 typedef struct vae_elbo_args {
   int32_t kind;            /* vae_loss_kind */
@@ -299,6 +299,17 @@ typedef struct vae_elbo_args {
    *   head_coef = 2 (dL/dsse_i = 1: no 1/(B*img_elems)), kl_coef = kld_weight (no 1/B);
    *   out = {loss, Reconstruction_Loss, -kld (as the reference reports it), kld};
    *   per_img stays the per-image mean MSE (experiment.py:60-62). */
+  /* VAE_LOSS_MIWAE (MIWAE, miwae.py:132-164): `samples` = M*K rows per image, M = estimates carried by
+   *   mmd_tiles (no field is added: the struct keeps its size), K = samples / M importance samples per
+   *   estimate; rows are b-major, then m, then k (row b*M*K + m*K + k, the order of miwae.py:105-106),
+   *   row r reads mu row r / samples.  With mse_r = sse[r] / img_elems:
+   *   lw[b,m,k] = mse_r + kld_weight*kld_b;  w = softmax_k(lw), inside each (b, m) group of K rows;
+   *   loss = mean_b mean_m Σ_k w*lw;  g_r = w_r (1 + lw_r - Σ_k w*lw) / (B*M) (the weights are not
+   *   detached);  head_coef[r] = g_r * 2 / img_elems, kl_coef[r] = g_r * kld_weight, per_img[r] = mse_r;
+   *   out = {loss, mean_r mse_r, -mean_b kld_b, mean_b kld_b}.
+   *   VAE_LOSS_IWAE is the one-group case: kind MIWAE with mmd_tiles = 1 gives the same bits.
+   *   VAE_E_BADSHAPE for estimates < 1, samples not a multiple of estimates, batch outside 1..1024
+   *   (each with its own reason; null mulv / head_coef / kl_coef are VAE_E_BADARG, checked first). */
 } vae_elbo_args;
 
 /* DIP-VAE's covariance penalty on the batch's latent means and its gradient ("DIP loss II",

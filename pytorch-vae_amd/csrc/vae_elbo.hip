@@ -19,7 +19,16 @@ using namespace vae;
 
 extern "C" int vae_elbo_fwd(const vae_elbo_args* a, void* stream) {
   if (!a || !a->sse || !a->out || !a->per_img) return fail(VAE_E_BADARG, "elbo_fwd: args");
-  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_DIP) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind < VAE_LOSS_VANILLA || a->kind > VAE_LOSS_MIWAE) return fail(VAE_E_BADARG, "elbo_fwd: kind");
+  if (a->kind == VAE_LOSS_MIWAE) {
+    // (the tensors before the shapes: mmd_tiles carries the estimates M, samples the M*K rows per image)
+    if (!a->mulv || !a->head_coef || !a->kl_coef) return fail(VAE_E_BADARG, "elbo_fwd: MIWAE mulv / head_coef / kl_coef");
+    const int rows = a->samples > 0 ? a->samples : 1;
+    if (a->mmd_tiles < 1) return fail(VAE_E_BADSHAPE, "elbo_fwd: MIWAE estimates %d below 1 (mmd_tiles)", a->mmd_tiles);
+    if (rows % a->mmd_tiles)
+      return fail(VAE_E_BADSHAPE, "elbo_fwd: MIWAE samples %d not a multiple of estimates %d", rows, a->mmd_tiles);
+    if (a->batch < 1 || a->batch > 1024) return fail(VAE_E_BADSHAPE, "elbo_fwd: MIWAE batch %d outside 1..1024", a->batch);
+  }
   if (a->kind == VAE_LOSS_DIP) {
     if (!a->mmd_partials || !a->mmd_out || a->mmd_tiles <= 0) return fail(VAE_E_BADARG, "elbo_fwd: dip partials / dip out (mmd_partials, mmd_out, mmd_tiles)");
     if (a->samples > 1) return fail(VAE_E_BADSHAPE, "elbo_fwd: DIP-VAE takes one sample");

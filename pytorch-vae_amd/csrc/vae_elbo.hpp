@@ -1,9 +1,63 @@
 // ELBO of the VAE family on one workgroup (vaehip.h vae_elbo_fwd; vanilla_vae.py:124-146,
-// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211, info_vae.py:128-148, dip_vae.py:125-164).
+// beta_vae.py:129-152, iwae.py:129-160, vq_vae.py:194-211, info_vae.py:128-148, dip_vae.py:125-164,
+// miwae.py:132-164).
 #pragma once
 #include "vae_common.hpp"
 
 namespace vae {
+
+// One importance-weighted group of K rows (IWAE's S samples of an image, one of MIWAE's M estimates):
+// Σ_k w lw with w = softmax_k(lw), lw_k = sse_k/img + kk (kk = M_N*kld_b), and the group's backward
+// seeds g_k = w_k (1 + lw_k - Σ w lw) / groups into head_coef / kl_coef at row r0 + k.  REG: K <=
+// ELBO_KREG, each sse read once and lw / exp kept in registers; else every pass recomputes them.
+constexpr int ELBO_KREG = 8;
+
+template <bool REG>
+__device__ __forceinline__ float elbo_group(const vae_elbo_args& a, const float* sse, long r0, int K, float kk,
+                                            float inv_img, float groups) {
+  if constexpr (REG) {
+    float lw[ELBO_KREG], e[ELBO_KREG];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < ELBO_KREG; ++k)
+      if (k < K) { lw[k] = sse[k] * inv_img + kk; mx = fmaxf(mx, lw[k]); }
+    float den = 0.f;
+#pragma unroll
+    for (int k = 0; k < ELBO_KREG; ++k)
+      if (k < K) { e[k] = expf(lw[k] - mx); den += e[k]; }
+    float wl = 0.f;
+#pragma unroll
+    for (int k = 0; k < ELBO_KREG; ++k)
+      if (k < K) wl += e[k] / den * lw[k];
+#pragma unroll
+    for (int k = 0; k < ELBO_KREG; ++k)
+      if (k < K) {
+        const float w = e[k] / den;
+        const float g = w * (1.f + lw[k] - wl) / groups;        // dL/dlw
+        a.head_coef[r0 + k] = g * 2.f * inv_img;
+        a.kl_coef[r0 + k] = g * a.kld_weight;
+      }
+    return wl;
+  } else {
+    float mx = -INFINITY;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, sse[k] * inv_img + kk);
+    float den = 0.f;
+    for (int k = 0; k < K; ++k) den += expf(sse[k] * inv_img + kk - mx);
+    float wl = 0.f;
+    for (int k = 0; k < K; ++k) {
+      const float lw = sse[k] * inv_img + kk;
+      wl += expf(lw - mx) / den * lw;
+    }
+    for (int k = 0; k < K; ++k) {
+      const float lw = sse[k] * inv_img + kk;
+      const float w = expf(lw - mx) / den;
+      const float g = w * (1.f + lw - wl) / groups;             // dL/dlw
+      a.head_coef[r0 + k] = g * 2.f * inv_img;
+      a.kl_coef[r0 + k] = g * a.kld_weight;
+    }
+    return wl;
+  }
+}
 
 // The loss of vaehip.h vae_elbo_fwd by one 256-thread workgroup (kld_row: 1024 floats of LDS, red:
 // 16) — run by elbo_kernel, and by the head backward's slab-reduction launch when the step fuses it
@@ -63,7 +117,7 @@ __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_ro
     }
     return;
   }
-  if (a.kind != VAE_LOSS_IWAE) {
+  if (a.kind != VAE_LOSS_IWAE && a.kind != VAE_LOSS_MIWAE) {
     const float recon = sse_tot / ((float)B * (float)a.img_elems);
     float loss, klc, kld_report;
     float rw = 1.f;                               // weight of the reconstruction term (and its seed)
@@ -97,33 +151,25 @@ __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_ro
     if (threadIdx.x == 0) { a.out[0] = loss; a.out[1] = recon; a.out[2] = kld_report; a.out[3] = kld_mean; }
     return;
   }
-  // IWAE: lw[b,s] = sse/img + M_N*kld_b ; w = softmax_s(lw) ; loss = mean_b Σ_s w lw
+  // IWAE / MIWAE (iwae.py:129-160, miwae.py:148-164): the B*M groups of K rows, row b*M*K + m*K + k
+  // (IWAE: M = 1, K = S); a thread owns a group.  lw = sse/img + M_N*kld_b ; w = softmax_k(lw) ;
+  // loss = mean over the groups of Σ_k w lw
+  const int M = a.kind == VAE_LOSS_MIWAE && a.mmd_tiles > 0 ? a.mmd_tiles : 1;
+  const int K = S / M, G = B * M;
   float lsum = 0.f;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    float mx = -INFINITY;
-    for (int s = 0; s < S; ++s) mx = fmaxf(mx, a.sse[b * S + s] * inv_img + a.kld_weight * kld_row[b]);
-    float den = 0.f;
-    for (int s = 0; s < S; ++s) den += expf(a.sse[b * S + s] * inv_img + a.kld_weight * kld_row[b] - mx);
-    float wl = 0.f;
-    for (int s = 0; s < S; ++s) {
-      const float lw = a.sse[b * S + s] * inv_img + a.kld_weight * kld_row[b];
-      wl += expf(lw - mx) / den * lw;
-    }
-    for (int s = 0; s < S; ++s) {
-      const float lw = a.sse[b * S + s] * inv_img + a.kld_weight * kld_row[b];
-      const float w = expf(lw - mx) / den;
-      const float g = w * (1.f + lw - wl) / (float)B;          // dL/dlw
-      a.head_coef[b * S + s] = g * 2.f * inv_img;
-      a.kl_coef[b * S + s] = g * a.kld_weight;
-    }
-    lsum += wl;
+  for (int g = threadIdx.x; g < G; g += 256) {
+    const int b = g / M;
+    const float* sse = a.sse + (long)g * K;
+    const float kk = a.kld_weight * kld_row[b];
+    if (K <= ELBO_KREG) lsum += elbo_group<true>(a, sse, (long)g * K, K, kk, inv_img, (float)G);
+    else lsum += elbo_group<false>(a, sse, (long)g * K, K, kk, inv_img, (float)G);
   }
   for (int off = 32; off > 0; off >>= 1) lsum += __shfl_xor(lsum, off);
   __syncthreads();
   if (lane == 0) red[2][wv] = lsum;
   __syncthreads();
   if (threadIdx.x == 0) {
-    a.out[0] = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) / (float)B;
+    a.out[0] = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) / (float)G;
     a.out[1] = sse_tot * inv_img / (float)(B * S);
     a.out[2] = -kld_mean;
     a.out[3] = kld_mean;

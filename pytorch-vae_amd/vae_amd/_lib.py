@@ -24,6 +24,7 @@ ABI_VERSION = 26
 F32, BF16 = 0, 1
 X_NONE, X_ACT, X_BN_ACT, X_BN_DY = 0, 1, 2, 3
 LOSS_VANILLA, LOSS_BETA_H, LOSS_BETA_B, LOSS_IWAE, LOSS_VQ, LOSS_INFO, LOSS_DIP = 0, 1, 2, 3, 4, 5, 6
+LOSS_MIWAE = 7                    # (its estimates M travel in ElboArgs.mmd_tiles: no new field)
 MMD_IMQ, MMD_RBF = 0, 1                                          # vaehip.h enum vae_mmd_kind
 
 

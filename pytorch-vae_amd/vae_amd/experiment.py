@@ -70,7 +70,9 @@ class VAEXperiment:
     def per_image_mse(recon: Tensor, input: Tensor) -> Tensor:
         """experiment.py:58-62: mse(recon, input, reduction='none').mean([1,2,3]).  IWAE's
         [B,S,C,H,W] reconstructions (where the reference's broadcast fails)
-        are scored per image averaged over the samples."""
+        are scored per image averaged over the samples, MIWAE's [B,M,K,C,H,W] over its M*K rows."""
+        if recon.dim() == 6:
+            return ((recon - input[:, None, None]) ** 2).mean(dim=[1, 2, 3, 4, 5])
         if recon.dim() == 5:
             return ((recon - input.unsqueeze(1)) ** 2).mean(dim=[1, 2, 3, 4])
         return F.mse_loss(recon, input, reduction='none').mean(dim=[1, 2, 3])

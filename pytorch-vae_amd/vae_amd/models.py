@@ -8,11 +8,12 @@ Mirrors the reference interface (paths relative to the reference root):
   IWAE                    models/iwae.py:8-188      (num_samples; row-major b*S+s latent order)
   InfoVAE                 models/info_vae.py:8-256  (MMD term on vae_mmd_fwd; imq / rbf kernels)
   DIPVAE                  models/dip_vae.py:8-191   (covariance penalty of the means on vae_dip_fwd)
+  MIWAE                   models/miwae.py:8-192     (num_estimates x num_samples; rows in b, m, k order)
   VQVAE                   models/vq_vae.py:73-219   (VectorQuantizer, residual stacks; vae_amd/vq.py)
   vae_models registry     models/__init__.py:35-56
 
 `forward(x)` runs the HIP encoder/decoder (libvaehip.so) and returns the reference's list
-([recons, input, mu, log_var], IWAE: [recons, input, mu, log_var, z, eps]).  `loss_function`
+([recons, input, mu, log_var], IWAE / MIWAE: [recons, input, mu, log_var, z, eps]).  `loss_function`
 called on that list (what experiment.VAEXperiment.training_step does) runs the ELBO on the GPU
 (vae_elbo_fwd, `_HipELBO`) and returns the reference's dict; its backward is the fused HIP
 backward seeded by the kernel's coefficients — no dL/drecon tensor is materialised.  On any
@@ -621,6 +622,83 @@ class DIPVAE(_HipVAE):
         return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'KLD': -kld_loss, 'DIP_Loss': dip_loss}
 
 
+class MIWAE(_HipVAE):
+    """models/miwae.py:8-192 on libvaehip: M = num_estimates independent importance-weighted estimates of
+    K = num_samples samples per image.  The decoder is batched at B*M*K rows in b, m, k order
+    (miwae.py:105-106); the loss is IWAE's self-normalised weighting inside each group of K, averaged
+    over M and B (VAE_LOSS_MIWAE)."""
+
+    def __init__(self, in_channels: int, latent_dim: int, hidden_dims: List = None, num_samples: int = 5,
+                 num_estimates: int = 5, **kwargs) -> None:
+        self.samples = num_samples * num_estimates          # rows per image
+        super().__init__(in_channels, latent_dim, hidden_dims, **kwargs)
+        self.num_samples = num_samples
+        self.num_estimates = num_estimates
+
+    def _loss_config(self) -> dict:
+        return dict(loss="miwae", samples=self.num_samples, estimates=self.num_estimates)
+
+    def _dropin_config(self) -> dict:
+        return self._loss_config()
+
+    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
+        """miwae.py:124-130: [recons [B,M,K,C,H,W], input, mu [B,M,K,D], log_var [B,M,K,D], z, eps]."""
+        B, M, K, D = input.shape[0], self.num_estimates, self.num_samples, self.latent_dim
+        recon, mu, log_var, eps = self._run(input, kwargs.get("eps"))
+        mu_r = mu.repeat(M, K, 1, 1).permute(2, 0, 1, 3)    # [B x M x K x D], miwae.py:126-127
+        lv_r = log_var.repeat(M, K, 1, 1).permute(2, 0, 1, 3)
+        eps_r = eps.reshape(B, M, K, D)
+        z = eps_r * torch.exp(0.5 * lv_r) + mu_r
+        eps_ret = (z - mu_r) / lv_r                         # miwae.py:129 (returned, unused by the loss)
+        out = [recon.view(B, M, K, *recon.shape[1:]), input, mu_r, lv_r, z, eps_ret]
+        self._remember(out)
+        return out
+
+    def decode(self, z: Tensor) -> Tensor:
+        """miwae.py:98-112: [B,M,K,D] -> [B,M,K,C,H,W].  A row count that is no multiple of this
+        model's M*K (sample(): [n,1,1,D]) is decoded by a one-row-per-image plan."""
+        lead = tuple(z.shape[:-1])
+        rows = z.reshape(-1, self.latent_dim).shape[0]
+        if rows % self.samples == 0:
+            recon = super().decode(z)
+        else:
+            key = ("rows", rows, self.training)
+            if key not in self._plans:
+                self._plans[key] = StepPlan(self.net, rows, loss="vanilla", fused_loss=False, training=self.training)
+            plan, st = self._plans[key], L.stream_ptr()
+            self.net.sync_lowp()
+            plan.z.copy_(z.detach().reshape(plan.z.shape))
+            L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
+            plan.decode(st)
+            recon = plan.recon.clone()
+        return recon.view(*lead, *recon.shape[1:])
+
+    def loss_function(self, *args, **kwargs) -> dict:
+        """miwae.py:132-164."""
+        g = self._gpu_loss(args, "miwae", kld_weight=kwargs['M_N'])
+        if g is not None:
+            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2]}
+        recons, input, mu, log_var = args[0], args[1], args[2], args[3]
+        input = input.repeat(self.num_estimates, self.num_samples, 1, 1, 1, 1).permute(2, 0, 1, 3, 4, 5)
+        kld_weight = kwargs['M_N']
+        log_p_x_z = ((recons - input) ** 2).flatten(3).mean(-1)                       # [B x M x K]
+        kld_loss = -0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=3)
+        log_weight = (log_p_x_z + kld_weight * kld_loss)
+        weight = F.softmax(log_weight, dim=-1)
+        loss = torch.mean(torch.mean(torch.sum(weight * log_weight, dim=-1), dim=-2), dim=0)
+        return {'loss': loss, 'Reconstruction_Loss': log_p_x_z.mean(), 'KLD': -kld_loss.mean()}
+
+    def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
+        """miwae.py:166-182."""
+        z = torch.randn(num_samples, 1, 1, self.latent_dim)
+        z = z.to(current_device)
+        return self.decode(z).squeeze()
+
+    def generate(self, x: Tensor, **kwargs) -> Tensor:
+        """miwae.py:184-192: the first reconstruction of every image."""
+        return self.forward(x)[0][:, 0, 0, :]
+
+
 class MSSIM(nn.Module):
     """models/mssim_vae.py:182-282: the differentiable MS-SSIM loss 1 - Π cs_l^w_l · ssim_L^w_L over five
     levels (11x11 window, avg-pool 2x2 between levels, size_average, dynamic range 1, normalised
@@ -960,7 +1038,7 @@ class VQVAE(BaseVAE):
 
 # models/__init__.py:35-56: the families on the MI355X path; the others raise on use.
 _ON_PATH = {'VanillaVAE': VanillaVAE, 'BetaVAE': BetaVAE, 'IWAE': IWAE, 'VQVAE': VQVAE, 'Autoencoder': Autoencoder,
-            'InfoVAE': InfoVAE, 'DIPVAE': DIPVAE}
+            'InfoVAE': InfoVAE, 'DIPVAE': DIPVAE, 'MIWAE': MIWAE}
 _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 'DIPVAE', 'BetaVAE', 'InfoVAE',
                     'WAE_MMD', 'VampVAE', 'GammaVAE', 'MSSIMVAE', 'JointVAE', 'BetaTCVAE', 'FactorVAE',
                     'LogCoshVAE', 'VanillaVAE', 'ConditionalVAE', 'CategoricalVAE', 'Autoencoder']
@@ -969,7 +1047,7 @@ _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 
 def _not_on_path(name):
     def ctor(*args, **kwargs):
         raise NotImplementedError(f"{name} is not on the MI355X training path of this build "
-                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE, DIPVAE are; "
+                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE, DIPVAE, MIWAE are; "
                                   f"DESIGN.md §7)")
     return ctor
 

@@ -71,7 +71,10 @@ class VAENet(NetBase):
 class StepPlan(PlanBase):
     """All buffers and prebuilt launches of one training step for a fixed batch shape.
 
-    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae' | 'info' | 'dip';  samples: IWAE S (decoder batch B*S).
+    loss: 'vanilla' | 'betaH' | 'betaB' | 'iwae' | 'info' | 'dip' | 'miwae';  samples: IWAE S (decoder
+    batch B*S).
+    'miwae' (MIWAE, models/miwae.py:124-164) takes samples = K and estimates = M: S = M*K rows per image
+    in b, m, k order, IWAE's weighting inside each group of K (VAE_LOSS_MIWAE).
     'info' (InfoVAE, models/info_vae.py:128-229) takes alpha, beta, reg_weight, kernel_type and
     latent_var; its MMD term runs on vae_mmd_fwd right after the reparameterization.
     'dip' (DIP-VAE, models/dip_vae.py:125-164) takes lambda_diag and lambda_offdiag; its covariance
@@ -88,7 +91,7 @@ class StepPlan(PlanBase):
                  pad_rgb: bool = True, materialise: bool = True, mat_min_flops: float = MAT_MIN_FLOPS,
                  batch_wgrads: bool = True, alpha: float = -0.5, reg_weight: float = 100.0,
                  kernel_type: str = "imq", latent_var: float = 2.0, lambda_diag: float = 10.0,
-                 lambda_offdiag: float = 5.0):
+                 lambda_offdiag: float = 5.0, estimates: Optional[int] = None):
         # Route options (explicit arguments; every non-default route has a GPU test,
         # tests/test_gpu_routes.py): latent_kernels / head_kernels / pad_rgb / materialise /
         # batch_wgrads = False keep the generic per-op calls in place of the dedicated bottleneck
@@ -122,7 +125,18 @@ class StepPlan(PlanBase):
         # the weight-gradient call's first workgroup writes dL/dgamma, dL/dbeta and the conv
         # bias gradient (closed form).  Eval mode keeps vae_bn_finalize (running statistics).
         self.bn_in_consumer = bn_in_consumer and training
-        self.S = samples if loss == "iwae" else 1
+        # estimates (MIWAE's M): S = M*K rows per image; every other loss has one group of `samples`
+        if estimates is not None and loss != "miwae":
+            raise ValueError(f"estimates is MIWAE's argument, not loss {loss!r}'s")
+        self.M = 1
+        if loss == "miwae":
+            self.M = 1 if estimates is None else int(estimates)
+            if self.M < 1 or int(samples) < 1:
+                raise ValueError(f"StepPlan(loss='miwae') needs samples >= 1 and estimates >= 1, "
+                                 f"got {samples} and {estimates}")
+            if not 1 <= batch <= 1024:
+                raise ValueError(f"StepPlan(loss='miwae') takes 1..1024 images a batch (vae_elbo_fwd), got {batch}")
+        self.S = samples if loss == "iwae" else (self.M * int(samples) if loss == "miwae" else 1)
         self.loss_kind = self.LOSS_KINDS[loss]
         self.kld_weight, self.beta, self.gamma = kld_weight, beta, gamma
         if kernel_type not in MMD_KINDS:
@@ -585,6 +599,8 @@ class StepPlan(PlanBase):
             e.mmd_tiles, e.mmd_partials, e.mmd_out = self._mmd_tiles, self.mmd_ws.data_ptr(), self.mmd.data_ptr()
         if self.dip_ws is not None:        # (VAE_LOSS_DIP reads its partials through the same three fields)
             e.mmd_tiles, e.mmd_partials, e.mmd_out = self._dip_tiles, self.dip_ws.data_ptr(), self.dip.data_ptr()
+        if self.loss_kind == L.LOSS_MIWAE:  # (VAE_LOSS_MIWAE: the tile count is its estimates M)
+            e.mmd_tiles = self.M
         self.n_decode1, self.elbo_args = len(F), e
         # elbo_in_head: the loss evaluated by the head backward (vaehip.h vae_head_args.elbo: one
         # extra workgroup of its filter-partial reduction, the seed coefficient a constant) instead
@@ -902,7 +918,7 @@ class StepPlan(PlanBase):
     # and seeds the backward from the kernel's coefficients (seed_fused) instead of autograd's
     # dL/drecon and dL/d[mu|log_var].
     LOSS_KINDS = {"vanilla": L.LOSS_VANILLA, "betaH": L.LOSS_BETA_H, "betaB": L.LOSS_BETA_B,
-                  "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO, "dip": L.LOSS_DIP}
+                  "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO, "dip": L.LOSS_DIP, "miwae": L.LOSS_MIWAE}
 
     def run_elbo(self, stream, loss: str, kld_weight: float, beta: float = 4.0, gamma: float = 1000.0,
                  c_max: float = 25.0, c_stop_iter: float = 1e5, num_iter: Optional[int] = None,
@@ -912,7 +928,12 @@ class StepPlan(PlanBase):
         per-row KL gradient coefficient (the backward seeds)."""
         e = self.elbo_args
         e.kind = self.LOSS_KINDS[loss]
-        if (e.kind == L.LOSS_IWAE) != (self.S > 1):
+        if e.kind == L.LOSS_MIWAE:
+            # (M*K rows per image in b, m, k order; M = K = 1 is the plain ELBO on one sample)
+            if self.loss_kind != L.LOSS_MIWAE:
+                raise ValueError("run_elbo('miwae') needs a plan built with loss='miwae'")
+            e.mmd_tiles = self.M
+        elif (e.kind == L.LOSS_IWAE) != (self.S > 1):
             raise ValueError(f"loss {loss!r} on a plan with {self.S} samples per image")
         e.kld_weight, e.beta, e.gamma, e.c_max, e.c_stop_iter = kld_weight, beta, gamma, c_max, c_stop_iter
         if num_iter is not None:
