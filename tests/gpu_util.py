@@ -16,7 +16,10 @@ def to_nchw(t_nhwc):
 class BNState:
     """A pre-BN NHWC tensor y plus BN params and the producer-side sums the kernels read."""
 
-    def __init__(self, y_nchw, shift=None, seed=0, dtype=torch.float32):
+    def __init__(self, y_nchw, shift=None, seed=0, dtype=torch.float32, reps=1, rstride=None):
+        """reps > 1: the sums (and the dgamma / dbeta handed to xf()) are spread over `reps` unequal
+        replica rows `rstride` floats apart (default C) with NaN between them, as bn_ref.split_replicas
+        makes them; the totals stay in .sum / .sumsq."""
         g = torch.Generator().manual_seed(seed)
         C = y_nchw.shape[1]
         self.y_nchw = y_nchw
@@ -28,7 +31,17 @@ class BNState:
         self.sumsq = (d * d).sum(dim=(0, 2, 3)).float()
         self.count = y_nchw.numel() // C
         self.dev = {k: getattr(self, k).cuda() for k in ("gamma", "beta", "shift", "sum", "sumsq")}
+        self.reps, self.rstride = reps, (C if rstride is None else rstride)
+        self._gen, self._keep = torch.Generator().manual_seed(seed + 1), []
+        if reps > 1:
+            for k in ("sum", "sumsq"):
+                self.dev[k] = self.replicated(getattr(self, k))
         self.y_dev = nhwc(y_nchw, dtype)
+
+    def replicated(self, total):
+        """A [C] total as this state's replica rows on the device."""
+        from bn_ref import split_replicas
+        return split_replicas(total.detach().cpu(), self.reps, self.rstride, self._gen).contiguous().cuda()
 
     def act_ref(self):
         """lrelu(BN_train(y)) in PyTorch, NCHW fp32 CPU."""
@@ -43,7 +56,12 @@ class BNState:
         x.shift = self.dev["shift"].data_ptr()
         x.gamma = self.dev["gamma"].data_ptr()
         x.beta = self.dev["beta"].data_ptr()
+        if self.reps > 1:
+            x.reps, x.rstride = self.reps, self.rstride
         if kind in (L.X_BN_DY,):
+            if self.reps > 1:
+                dgamma, dbeta = self.replicated(dgamma), self.replicated(dbeta)
+                self._keep += [dgamma, dbeta]
             x.dgamma = dgamma.data_ptr()
             x.dbeta = dbeta.data_ptr()
         if aux is not None:

@@ -343,11 +343,14 @@ def test_cgemm_convT2d_bwd_data(shape):
 # bias gradient and dL/dgamma, dL/dbeta published by the first workgroup.
 
 class BN:
-    """A stored pre-BN tensor with consistent statistics (reps=1 sums over N*H*W, shift = the
-    producing conv's bias) as the producing kernels leave them."""
+    """A stored pre-BN tensor with consistent statistics (sums over N*H*W, shift = the producing
+    conv's bias) as the producing kernels leave them: one copy, or with reps > 1 spread over `reps`
+    unequal replica rows `rstride` floats apart (default C; bn_ref.split_replicas, NaN between the
+    rows), the dgamma / dbeta handed to xf() included."""
 
-    def __init__(self, y, g, shift=None):
+    def __init__(self, y, g, shift=None, reps=1, rstride=None):
         C = y.shape[1]
+        self.reps, self.rstride, self.g = reps, (C if rstride is None else rstride), g
         self.y = y
         self.gamma = 0.7 + 0.6 * torch.rand(C, generator=g)
         self.beta = (torch.rand(C, generator=g) - 0.5) * 0.2
@@ -362,13 +365,14 @@ class BN:
         C = self.gamma.numel()
         x = L.Xform(kind=kind, channels=C, slope=SLOPE, count=float(self.count), eps=1e-5, momentum=0.1)
         for name in ("sum", "sumsq", "shift", "gamma", "beta"):
-            t = getattr(self, name).float().cuda()
+            t = getattr(self, name).float()
+            t = (self.spread(t) if name in ("sum", "sumsq") else t).cuda()
             self.keep.append(t)
             setattr(x, name, t.data_ptr())
-        x.reps, x.rstride = 1, C
+        x.reps, x.rstride = self.reps, self.rstride
         if dgamma is not None:
             for name, t in (("dgamma", dgamma), ("dbeta", dbeta)):
-                t = t.float().cuda()
+                t = self.spread(t.float()).cuda()
                 self.keep.append(t)
                 setattr(x, name, t.data_ptr())
         if dgamma_out is not None:
@@ -377,16 +381,23 @@ class BN:
             x.aux = aux_dev.data_ptr()
         return x
 
+    def spread(self, total):
+        if self.reps <= 1:
+            return total
+        from bn_ref import split_replicas
+        return split_replicas(total, self.reps, self.rstride, self.g).contiguous()
+
     def act(self, rnd=bf):
         z = F.batch_norm(self.y.double(), None, None, self.gamma.double(), self.beta.double(), True, 0.1, 1e-5)
         return rnd(F.leaky_relu(z, SLOPE).float())
 
 
-def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, fp32=False, odd_dy=False):
+def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, fp32=False, odd_dy=False, reps=1):
     """One bf16 weight-gradient call's arguments (kernel-side operands) and its fp64 reference.
     fp32: the parity mode's call instead (fp32 operands, nothing rounded to bf16, every partial sum
     added in a fixed order: vae_conv_args.deterministic), against the same fp64 reference.
-    odd_dy: the stored gradient starts 8 bytes past a 16-byte boundary."""
+    odd_dy: the stored gradient starts 8 bytes past a 16-byte boundary.  reps: replicas of both
+    BatchNorms' statistics (BN)."""
     L = _L()
     bf = (lambda t: t.float()) if fp32 else globals()["bf"]
     nhwc = (lambda t: t.permute(0, 2, 3, 1).contiguous().to("cuda", torch.float32)) if fp32 else globals()["nhwc"]
@@ -400,8 +411,8 @@ def prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, se
     xst = bf(torch.randn(N, cin, hw, hw, generator=g) * 1.3 + 0.2)
     yst = bf(torch.randn(N, cout, P, P, generator=g) * 1.1 - 0.1)      # pre-BN output (BN_DY aux)
     gst = bf(torch.randn(N, cout, P, P, generator=g))                   # dL/dz of its BatchNorm
-    bnx = BN(xst, g)
-    bny = BN(yst, g, shift=torch.randn(cout, generator=g) * 0.1)
+    bnx = BN(xst, g, reps=reps)
+    bny = BN(yst, g, shift=torch.randn(cout, generator=g) * 0.1, reps=reps)
     # operands as the kernel forms them
     if x_kind == L.X_BN_ACT:
         act = bnx.act(bf)
@@ -476,10 +487,10 @@ def check_wgrad(w):
         assert e_dg < 1e-5 and e_dbt < 1e-5
 
 
-def run_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, odd_dy=False):
+def run_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed=3, odd_dy=False, reps=1):
     """One standalone bf16 weight-gradient call (its queried workspace given) against fp64."""
     L = _L()
-    w = prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed, odd_dy=odd_dy)
+    w = prep_wgrad(transposed, N, cin, cout, hw, stride, R, pad, x_kind, dy_kind, seed, odd_dy=odd_dy, reps=reps)
     a, fn = w["a"], w["fn"]
     ws = give_workspace(a, fn)           # 4 bytes when the plan takes none
     L.call(fn, ctypes.byref(a), torch.cuda.current_stream().cuda_stream)
@@ -498,6 +509,19 @@ WGRAD = [  # N, cin, cout, hw (conv input), stride, R, pad
 def test_wgemm_conv2d_bn(shape):
     L = _L()
     run_wgrad(False, *shape, L.X_NONE if shape[1] == 8 else L.X_BN_ACT, L.X_BN_DY)
+
+
+@pytest.mark.parametrize("transposed,shape,reps", [
+    (False, WGRAD[1], 4),                 # 64 -> 128 channels, 4 replicas (a plan's count at 64): one-round build
+    (True, (8, 128, 64, 8, 2, 3, 1), 4),  # WGRAD_T[1]
+    (False, WGRAD[1], 32),                # reps·C = 2048 and 4096 > 1024: the plain loop, two rounds of replicas
+])
+def test_wgemm_bn_replicated_stats(transposed, shape, reps):
+    """test_wgemm_conv2d_bn / test_wgemm_convT2d_bn with the statistics of both operands' BatchNorms in
+    replicas (Σ, Σ² of x; Σ, Σ², Σg·x̂, Σg of y), also for the first workgroup's closed-form bias
+    gradient and dgamma_out / dbeta_out."""
+    L = _L()
+    run_wgrad(transposed, *shape, L.X_BN_ACT, L.X_BN_DY, reps=reps)
 
 
 def test_wgemm_conv2d_vq_shapes():
@@ -565,11 +589,20 @@ def test_wgemm_taps_pixel_tail(shape, N):
 
 def test_cgemm_fwd_table_built_in_kernel():
     """Forward conv with BN_ACT from the raw statistics (no table): tab_build + running stats."""
+    _cgemm_fwd_table_built_in_kernel(1)
+
+
+def test_cgemm_fwd_table_built_from_replicated_stats():
+    """The same from 4 replicas of the statistics (the plans' count at 64 channels)."""
+    _cgemm_fwd_table_built_in_kernel(4)
+
+
+def _cgemm_fwd_table_built_in_kernel(reps):
     L = _L()
     g = torch.Generator().manual_seed(9)
     N, cin, cout, hw = 8, 64, 128, 16
     y = bf(torch.randn(N, cin, hw, hw, generator=g) * 0.9 + 0.4)
-    bn = BN(y, g, shift=torch.randn(cin, generator=g) * 0.05)
+    bn = BN(y, g, shift=torch.randn(cin, generator=g) * 0.05, reps=reps)
     w = bf(torch.randn(cout, cin, 3, 3, generator=g) * 0.1)
     ref = F.conv2d(bn.act().double(), w.double(), None, stride=2, padding=1)
     out = torch.empty(N, hw // 2, hw // 2, cout, device="cuda", dtype=torch.bfloat16)

@@ -29,11 +29,24 @@ def _stream():
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("cin,cout,hw", [(32, 64, 16), (64, 32, 8), (16, 48, 12)])
 def test_conv2d_fwd_bnact_and_stats(dtype, cin, cout, hw, split):
+    _conv2d_fwd_bnact_and_stats(dtype, cin, cout, hw, split)
+
+
+@pytest.mark.parametrize("split", [0, 3])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("cin,cout,hw,reps,rstride", [(32, 64, 16, 8, None), (16, 48, 12, 32, 24)])
+def test_conv2d_fwd_bnact_replicated_stats(dtype, cin, cout, hw, split, reps, rstride):
+    """test_conv2d_fwd_bnact_and_stats with the input BatchNorm's sums in replicas: 8 at 32 channels (a
+    plan's count) and 32 rows 24 floats apart at 16 channels (more than any plan asks for)."""
+    _conv2d_fwd_bnact_and_stats(dtype, cin, cout, hw, split, reps, rstride)
+
+
+def _conv2d_fwd_bnact_and_stats(dtype, cin, cout, hw, split, reps=1, rstride=None):
     L = _L()
     torch.manual_seed(0)
     N = 4
     y_prev = torch.randn(N, cin, hw, hw) * 1.5 + 0.3
-    bn = BNState(y_prev, shift=torch.randn(cin) * 0.1, dtype=dtype)
+    bn = BNState(y_prev, shift=torch.randn(cin) * 0.1, dtype=dtype, reps=reps, rstride=rstride)
     w = torch.randn(cout, cin, 3, 3) * 0.1
     b = torch.randn(cout) * 0.1
     ref = F.conv2d(bn.act_ref(), w, b, stride=2, padding=1)
@@ -138,6 +151,18 @@ def test_conv_backward_plain(dtype, transposed):
 def test_conv2d_backward_bn(dtype, split):
     """dy through BN_DY (BN-backward on load) and dx through the BN_ACT epilogue, vs autograd
     of conv(lrelu(bn(y_prev))) -> bn -> (upstream grad)."""
+    _conv2d_backward_bn(dtype, split)
+
+
+@pytest.mark.parametrize("split", [0, 2])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_conv2d_backward_bn_replicated_stats(dtype, split):
+    """test_conv2d_backward_bn with the statistics of both BatchNorms (Σ, Σ², and Σg·x̂, Σg of the
+    current one) in 4 replicas."""
+    _conv2d_backward_bn(dtype, split, reps=4)
+
+
+def _conv2d_backward_bn(dtype, split, reps=1):
     L = _L()
     torch.manual_seed(4)
     N, cin, cout, hw = 4, 32, 64, 8
@@ -155,10 +180,10 @@ def test_conv2d_backward_bn(dtype, split):
     z.backward(gz)
     # device state: previous BN, current BN, and the upstream g = dL/dz (what the next
     # layer's epilogue would have produced) with Σg, Σg·x̂ (== dβ, dγ of the current BN)
-    bnp = BNState(y_prev.detach(), dtype=dtype); bnp.gamma, bnp.beta = g_prev, b_prev
+    bnp = BNState(y_prev.detach(), dtype=dtype, reps=reps); bnp.gamma, bnp.beta = g_prev, b_prev
     bnp.dev["gamma"], bnp.dev["beta"] = g_prev.cuda(), b_prev.cuda()
     yv = y.detach()
-    bnc = BNState(yv, shift=bias.detach(), dtype=dtype); bnc.gamma, bnc.beta = g_cur, b_cur
+    bnc = BNState(yv, shift=bias.detach(), dtype=dtype, reps=reps); bnc.gamma, bnc.beta = g_cur, b_cur
     bnc.dev["gamma"], bnc.dev["beta"] = g_cur.cuda(), b_cur.cuda()
     mean = yv.mean((0, 2, 3), keepdim=True); var = yv.var((0, 2, 3), unbiased=False, keepdim=True)
     xh = (yv - mean) / torch.sqrt(var + 1e-5)
@@ -257,7 +282,17 @@ def test_head_valu_route(dtype, C, fused):
         assert "head_bwd_data_kernel" in data[0] and f"Li{C}E" in data[0], names   # (the mangled <T, C>)
 
 
-def _head_case(dtype, fused, C, N, H, mfma):
+@pytest.mark.parametrize("fused", [False, True])
+@pytest.mark.parametrize("dtype,C,reps", [(torch.float32, 32, 8), (torch.bfloat16, 32, 8), (torch.bfloat16, 64, 4),
+                                          (torch.bfloat16, 128, 2), (torch.bfloat16, 128, 32)])
+def test_head_fwd_bwd_replicated_stats(dtype, fused, C, reps):
+    """test_head_fwd_bwd with the input BatchNorm's sums in replicas: the plans' counts (8 at 32
+    channels, 4 at 64, 2 at 128) and 32 at 128 channels, which bn_fast_ok declines (head_tables'
+    plain loop)."""
+    _head_case(dtype, fused, C, 2, 64, mfma=dtype == torch.bfloat16, reps=reps)
+
+
+def _head_case(dtype, fused, C, N, H, mfma, reps=1):
     """One head forward + backward at [N, C, H, H] against autograd; returns the launch log.  mfma:
     the call runs the bf16 MFMA kernels, whose reconstruction is also held against a reference
     with their operand rounding."""
@@ -273,7 +308,7 @@ def _head_case(dtype, fused, C, N, H, mfma):
     tgt = torch.rand(N, 3, H, H)
     loss = F.mse_loss(rec, tgt)
     loss.backward()
-    bn = BNState(y_prev.detach(), dtype=dtype); bn.gamma, bn.beta = gam, bet
+    bn = BNState(y_prev.detach(), dtype=dtype, reps=reps); bn.gamma, bn.beta = gam, bet
     bn.dev["gamma"], bn.dev["beta"] = gam.cuda(), bet.cuda()
     wd = w.detach().permute(0, 2, 3, 1).contiguous().cuda(); bd = b.detach().cuda()
     tg = tgt.cuda()
