@@ -450,6 +450,7 @@ class TrainStep:
 
     def mmd_term(self) -> float:
         """InfoVAE: the 'MMD' entry of the last step's loss dict (extra_term)."""
-        if self.plan.loss_kind != L.LOSS_INFO:
+        term = self.extra_term()
+        if term is None or term[0] != "MMD":
             raise ValueError("this step's loss has no MMD term")
-        return self.extra_term()[1]
+        return term[1]

@@ -42,6 +42,8 @@ from . import _lib as L
 from .net import StepPlan, VAENet
 
 Tensor = torch.Tensor
+# what of a model's _loss_config are arguments of the loss itself (StepPlan.run_elbo); the rest shapes the plan
+_ELBO_KEYS = ("loss", "beta", "gamma", "max_capacity", "capacity_max_iter", "alpha", "reg_weight")
 
 
 class BaseVAE(nn.Module):
@@ -101,27 +103,31 @@ class BaseVAE(nn.Module):
         pass
 
 
+def _run_forward(plan, calls, **inputs):
+    """The head of every pass of a drop-in plan, then `calls` of its forward: refresh the bf16 weights
+    (the optimizer may have moved the fp32 master), copy `inputs` into the plan's buffers of those
+    names, vae_step_begin."""
+    st = L.stream_ptr()
+    plan.net.sync_lowp()
+    for name, t in inputs.items():
+        getattr(plan, name).copy_(t.detach())
+    L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
+    plan._run(calls, st)
+
+
 class _VAEStep(torch.autograd.Function):
     """Forward of the HIP network; backward = the fused HIP backward of the whole network."""
 
     @staticmethod
     def forward(ctx, flat: Tensor, x: Tensor, eps: Tensor, model: "_HipVAE"):
         plan = model._plan(x.shape[0])
-        st = L.stream_ptr()
-        model.net.sync_lowp()                          # optimizer may have moved the fp32 master
-        plan.x.copy_(x.detach().to(plan.x.dtype))
-        plan.eps.copy_(eps.detach().reshape(plan.eps.shape))
-        L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-        plan.forward(st)
+        _run_forward(plan, plan.fwd_calls, x=x, eps=eps.reshape(plan.eps.shape))
         plan.backward_done = False
         model.net.num_batches_tracked += 1
         ctx.plan = plan
         ctx.set_materialize_grads(False)
         D = model.latent_dim
-        recon = plan.recon.clone()
-        mu = plan.mulv[:, :D].clone()
-        log_var = plan.mulv[:, D:].clone()
-        return recon, mu, log_var
+        return plan.recon.clone(), plan.mulv[:, :D].clone(), plan.mulv[:, D:].clone()
 
     @staticmethod
     def backward(ctx, g_recon: Optional[Tensor], g_mu: Optional[Tensor], g_lv: Optional[Tensor]):
@@ -158,13 +164,12 @@ class _HipELBO(torch.autograd.Function):
         # the unscaled backward seeds of this loss (a repeated backward rescales from these)
         ctx.seeds = (plan.head_coef.clone(), plan.kl_coef.clone())
         loss, rl, kld = plan.out[0].clone(), plan.out[1].clone(), plan.out[2].clone()
-        # InfoVAE: a third seed, dmmd/dz (vae_mmd_fwd at run_elbo), applied scaled in the backward;
-        # the loss dict's MMD entry is a fourth output
-        ctx.mmd_seed = (plan.dz_mmd.clone(), plan.mmd_coef) if loss_kw["loss"] == "info" else None
-        # DIP-VAE: likewise d dip/d[mu | log_var] (vae_dip_fwd at run_elbo) and the DIP_Loss entry
-        ctx.dip_seed = plan.dmulv_dip.clone() if loss_kw["loss"] == "dip" else None
-        if ctx.mmd_seed is not None or ctx.dip_seed is not None:
-            fourth = plan.extra_term[1][0].clone()
+        # a plan with a latent term (terms.py): a third seed, the term's gradient as run_elbo left it,
+        # applied scaled in the backward; the term's loss-dict entry is a fourth output
+        ctx.term_seed = None
+        if plan.term is not None:
+            ctx.term_seed = plan.term.seed()
+            fourth = plan.term.value[0].clone()
             ctx.mark_non_differentiable(rl, kld, fourth)
             return loss, rl, kld, fourth
         ctx.mark_non_differentiable(rl, kld)
@@ -180,11 +185,8 @@ class _HipELBO(torch.autograd.Function):
         plan.backward_done = True
         torch.mul(ctx.seeds[0], g_loss, out=plan.head_coef)
         torch.mul(ctx.seeds[1], g_loss, out=plan.kl_coef)
-        if ctx.mmd_seed is not None:
-            plan.dz_mmd.copy_(ctx.mmd_seed[0])
-            plan.seed_mmd(g_loss, ctx.mmd_seed[1], L.stream_ptr())
-        if ctx.dip_seed is not None:
-            plan.seed_dip(g_loss, ctx.dip_seed)
+        if ctx.term_seed is not None:
+            plan.term.apply_seed(ctx.term_seed, g_loss, L.stream_ptr())
         plan.seed_fused(True)
         try:
             plan.backward(L.stream_ptr())
@@ -238,11 +240,16 @@ class _HipVAE(BaseVAE):
                           img_size=img_size, dtype=dtype, device=device, generator=gen)
         self.flat = nn.Parameter(self.net.params)      # shares storage with the kernels' buffer
         self._plans: Dict[int, StepPlan] = {}
-        self._last = None                              # (plan, input, recon, mu, log_var) of forward
+        self._last = None                              # (plan, returned tensors, mu, log_var) of forward
 
     def _loss_config(self) -> dict:
         """StepPlan loss arguments of this model's loss_function."""
         return dict(loss="iwae" if self.samples > 1 else "vanilla", samples=self.samples)
+
+    def _dropin_config(self) -> dict:
+        """StepPlan loss arguments of the drop-in plans: the plan has to hold what the loss needs
+        (a loss chosen at loss_function time takes the vanilla plan: BetaVAE, Autoencoder)."""
+        return self._loss_config()
 
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
@@ -263,16 +270,23 @@ class _HipVAE(BaseVAE):
         return TrainStep(self.net, plan, opt, graph=graph, process_group=process_group, device_eps=device_eps,
                          device_prior=device_prior)
 
-    def _gpu_loss(self, args, loss: str, **kw):
-        """The loss dict terms from vae_elbo_fwd when `args` are exactly what this model's last
-        training forward returned (so its buffers hold them), else None (torch formula)."""
+    def _gpu_loss(self, args, **kw):
+        """The loss dict from vae_elbo_fwd when `args` are exactly what this model's last training
+        forward returned (so its buffers hold them), else None (torch formula).  The loss and its
+        weights are those of _loss_config; `kw`: kld_weight and what only the call knows."""
         last = self._last
-        if last is None or not self.training or not torch.is_grad_enabled() or len(args) < 4:
+        if last is None or not self.training or not torch.is_grad_enabled():
             return None
-        plan, inp, recon, mu, lv = last
-        if args[0] is not recon or args[1] is not inp or args[2] is not mu or args[3] is not lv:
+        plan, returned, mu, lv = last
+        if len(args) < len(returned) or any(a is not r for a, r in zip(args, returned)):
             return None
-        return _HipELBO.apply(self.flat, recon, mu, lv, plan, dict(loss=loss, **kw))
+        cfg = self._loss_config()
+        kw = {**{k: cfg[k] for k in _ELBO_KEYS if k in cfg}, **kw}
+        out = _HipELBO.apply(self.flat, returned[0], mu, lv, plan, kw)
+        d = dict(zip(plan.loss_names, out))
+        if plan.term is not None:
+            plan.term.place(d, out[3])
+        return d
 
     def _plan(self, batch: int, training: Optional[bool] = None) -> StepPlan:
         """Launch plan for a batch size: train-mode BatchNorm (batch statistics, running-stat
@@ -285,24 +299,11 @@ class _HipVAE(BaseVAE):
                                         training=training)
         return self._plans[key]
 
-    def _dropin_config(self) -> dict:
-        """StepPlan loss arguments of the drop-in plans (their loss is chosen at loss_function time;
-        the plan only has to hold what that loss needs)."""
-        return dict(loss="iwae" if self.samples > 1 else "vanilla", samples=self.samples)
-
-    def _eval_forward(self, input: Tensor, eps: Optional[Tensor]):
+    def _eval_forward(self, input: Tensor, eps: Tensor):
         """model.eval() forward (no autograd): encoder, reparameterization, decoder with running
         BatchNorm statistics (vanilla_vae.py:119-122 under eval())."""
-        B = input.shape[0]
-        if eps is None:
-            eps = torch.randn(B * self.samples, self.latent_dim, device=input.device)
-        plan = self._plan(B, False)
-        st = L.stream_ptr()
-        self.net.sync_lowp()
-        plan.x.copy_(input.detach().to(plan.x.dtype))
-        plan.eps.copy_(eps.detach().reshape(plan.eps.shape))
-        L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-        plan._run(plan.fwd_calls[:plan.n_decode1], st)
+        plan = self._plan(input.shape[0], False)
+        _run_forward(plan, plan.fwd_calls[:plan.n_decode1], x=input, eps=eps.reshape(plan.eps.shape))
         D = self.latent_dim
         return plan.recon.clone(), plan.mulv[:, :D].clone(), plan.mulv[:, D:].clone(), eps
 
@@ -323,38 +324,39 @@ class _HipVAE(BaseVAE):
 
     def encode(self, input: Tensor) -> List[Tensor]:
         plan = self._plan(input.shape[0])
-        st = L.stream_ptr()
-        self.net.sync_lowp()
-        plan.x.copy_(input.detach())
-        L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-        plan.encode(st)
+        _run_forward(plan, plan.fwd_calls[:plan.n_encode], x=input)
         D = self.latent_dim
         return [plan.mulv[:, :D].clone(), plan.mulv[:, D:].clone()]
 
     def decode(self, z: Tensor) -> Tensor:
-        rows = z.reshape(-1, self.latent_dim).shape[0]
-        plan = self._plan(rows // self.samples)
-        st = L.stream_ptr()
-        self.net.sync_lowp()
-        plan.z.copy_(z.detach().reshape(plan.z.shape))
-        L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-        plan.decode(st)
+        return self._decode(z, self._plan(z.reshape(-1, self.latent_dim).shape[0] // self.samples))
+
+    def _decode(self, z: Tensor, plan: StepPlan) -> Tensor:
+        _run_forward(plan, plan.fwd_calls[plan.n_decode0:plan.n_decode1], z=z.reshape(plan.z.shape))
         return plan.recon.clone()
 
-    def _remember(self, out):
-        """Keep the identity of a training forward's outputs for _gpu_loss (eval: forget)."""
-        if self.training and torch.is_grad_enabled() and out[0].grad_fn is not None:
-            self._last = (self._plan(out[1].shape[0]), out[1], out[0], out[2], out[3])
+    def _remember(self, returned, mu: Tensor, log_var: Tensor):
+        """Keep what a training forward returned — `returned`, the leading entries of its list
+        (recons, input, ...), the tensors loss_function must be handed back for _gpu_loss — and the
+        mu / log_var of that forward (in the list or behind it); eval: forget."""
+        if self.training and torch.is_grad_enabled() and returned[0].grad_fn is not None:
+            self._last = (self._plan(returned[1].shape[0]), tuple(returned), mu, log_var)
         else:
             self._last = None
 
     def _run(self, input: Tensor, eps: Optional[Tensor] = None):
+        if eps is None:                                 # torch.randn_like(std), vanilla_vae.py:116
+            eps = torch.randn(input.shape[0] * self.samples, self.latent_dim, device=input.device)
         if not self.training:
             return self._eval_forward(input, eps)
-        B = input.shape[0]
-        if eps is None:                                 # torch.randn_like(std), vanilla_vae.py:116
-            eps = torch.randn(B * self.samples, self.latent_dim, device=input.device)
         return _VAEStep.apply(self.flat, input, eps, self) + (eps,)
+
+    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
+        """vanilla_vae.py:119-122, beta_vae.py:124-127, dip_vae.py:120-123: [recons, input, mu, log_var]."""
+        recon, mu, log_var, _ = self._run(input, kwargs.get("eps"))
+        out = [recon, input, mu, log_var]
+        self._remember(out, mu, log_var)
+        return out
 
     def sample(self, num_samples: int, current_device: int, **kwargs) -> Tensor:
         """vanilla_vae.py:148-161."""
@@ -369,18 +371,12 @@ class _HipVAE(BaseVAE):
 class VanillaVAE(_HipVAE):
     """models/vanilla_vae.py:8-173 on libvaehip."""
 
-    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
-        recon, mu, log_var, _ = self._run(input, kwargs.get("eps"))
-        out = [recon, input, mu, log_var]
-        self._remember(out)
-        return out
-
     def loss_function(self, *args, **kwargs) -> dict:
         """vanilla_vae.py:124-146."""
         kld_weight = kwargs['M_N']
-        g = self._gpu_loss(args, "vanilla", kld_weight=kld_weight)
+        g = self._gpu_loss(args, kld_weight=kld_weight)
         if g is not None:
-            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2]}
+            return g
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         recons_loss = F.mse_loss(recons, input)
         kld_loss = torch.mean(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
@@ -403,17 +399,14 @@ class BetaVAE(_HipVAE):
         self.C_max = torch.Tensor([max_capacity])
         self.C_stop_iter = Capacity_max_iter
 
-    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
-        recon, mu, log_var, _ = self._run(input, kwargs.get("eps"))
-        out = [recon, input, mu, log_var]
-        self._remember(out)
-        return out
-
     def _loss_config(self) -> dict:
         if self.loss_type not in ('H', 'B'):
             raise ValueError('Undefined loss type.')
         return dict(loss="betaH" if self.loss_type == 'H' else "betaB", beta=float(self.beta), gamma=float(self.gamma),
                     max_capacity=float(self.C_max[0]), capacity_max_iter=float(self.C_stop_iter))
+
+    def _dropin_config(self) -> dict:
+        return _HipVAE._loss_config(self)       # (loss_type, beta and gamma are read at loss_function time)
 
     def fused_train_step(self, *args, **kwargs):
         step = super().fused_train_step(*args, **kwargs)
@@ -425,11 +418,9 @@ class BetaVAE(_HipVAE):
         self.num_iter += 1
         kld_weight = kwargs['M_N']
         if self.loss_type in ('H', 'B'):
-            g = self._gpu_loss(args, "betaH" if self.loss_type == 'H' else "betaB", kld_weight=kld_weight,
-                               beta=float(self.beta), gamma=float(self.gamma), c_max=float(self.C_max[0]),
-                               c_stop_iter=float(self.C_stop_iter), num_iter=self.num_iter)
+            g = self._gpu_loss(args, kld_weight=kld_weight, num_iter=self.num_iter)
             if g is not None:
-                return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2]}
+                return g
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         recons_loss = F.mse_loss(recons, input)
         kld_loss = torch.mean(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
@@ -463,14 +454,15 @@ class IWAE(_HipVAE):
         z = eps_r * torch.exp(0.5 * lv_r) + mu_r
         eps_ret = (z - mu_r) / lv_r                         # iwae.py:126 (returned, unused by the loss)
         out = [recon.view(B, S, *recon.shape[1:]), input, mu_r, lv_r, z, eps_ret]
-        self._remember(out)
+        self._remember(out[:4], mu_r, lv_r)
         return out
 
     def loss_function(self, *args, **kwargs) -> dict:
         """iwae.py:129-160."""
-        g = self._gpu_loss(args, "iwae", kld_weight=kwargs['M_N'])
+        # (loss: IWAE's also for num_samples = 1, whose plans are the vanilla ones and refuse it)
+        g = self._gpu_loss(args, kld_weight=kwargs['M_N'], loss="iwae")
         if g is not None:
-            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2]}
+            return g
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         input = input.repeat(self.num_samples, 1, 1, 1, 1).permute(1, 0, 2, 3, 4)
         kld_weight = kwargs['M_N']
@@ -506,18 +498,12 @@ class InfoVAE(_HipVAE):
         return dict(loss="info", alpha=float(self.alpha), beta=float(self.beta), reg_weight=float(self.reg_weight),
                     kernel_type=self.kernel_type, latent_var=float(self.z_var))
 
-    def _dropin_config(self) -> dict:
-        return self._loss_config()
-
     def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
         """info_vae.py:123-126: [recons, input, z, mu, log_var]."""
         recon, mu, log_var, eps = self._run(input, kwargs.get("eps"))
         z = eps.reshape(mu.shape) * torch.exp(0.5 * log_var) + mu
         out = [recon, input, z, mu, log_var]
-        if self.training and torch.is_grad_enabled() and recon.grad_fn is not None:
-            self._last = (self._plan(input.shape[0]), input, recon, mu, log_var, z)
-        else:
-            self._last = None
+        self._remember(out, mu, log_var)
         return out
 
     def loss_function(self, *args, **kwargs) -> dict:
@@ -528,13 +514,9 @@ class InfoVAE(_HipVAE):
         prior = kwargs.get("prior")
         if prior is None:
             prior = torch.randn_like(z)
-        last = self._last
-        if (last is not None and self.training and torch.is_grad_enabled() and recons is last[2] and input is last[1]
-                and z is last[5] and mu is last[3] and log_var is last[4]):
-            g = _HipELBO.apply(self.flat, recons, mu, log_var, last[0],
-                               dict(loss="info", kld_weight=kld_weight, beta=float(self.beta), alpha=float(self.alpha),
-                                    reg_weight=float(self.reg_weight), prior=prior))
-            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'MMD': g[3], 'KLD': g[2]}
+        g = self._gpu_loss(args, kld_weight=kld_weight, prior=prior)
+        if g is not None:
+            return g                                   # (MMD before KLD, as below: MmdTerm.place)
         batch_size = input.size(0)
         bias_corr = batch_size * (batch_size - 1)
         recons_loss = F.mse_loss(recons, input)
@@ -587,27 +569,16 @@ class DIPVAE(_HipVAE):
     def _loss_config(self) -> dict:
         return dict(loss="dip", lambda_diag=float(self.lambda_diag), lambda_offdiag=float(self.lambda_offdiag))
 
-    def _dropin_config(self) -> dict:
-        return self._loss_config()
-
-    def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
-        """dip_vae.py:120-123: [recons, input, mu, log_var]."""
-        recon, mu, log_var, _ = self._run(input, kwargs.get("eps"))
-        out = [recon, input, mu, log_var]
-        self._remember(out)
-        return out
-
     def loss_function(self, *args, **kwargs) -> dict:
         """dip_vae.py:125-164."""
         kld_weight = kwargs['M_N']
         last = self._last
-        # (the drop-in plan holds the lambdas it was built with: a model whose lambdas were changed
-        # afterwards takes the torch formula)
-        if last is not None and (last[0].lambda_diag, last[0].lambda_offdiag) == (float(self.lambda_diag),
-                                                                                 float(self.lambda_offdiag)):
-            g = self._gpu_loss(args, "dip", kld_weight=kld_weight)
+        # (the drop-in plan's term holds the lambdas it was built with: a model whose lambdas were
+        # changed afterwards takes the torch formula)
+        if last is not None and last[0].term.lambdas == (float(self.lambda_diag), float(self.lambda_offdiag)):
+            g = self._gpu_loss(args, kld_weight=kld_weight)
             if g is not None:
-                return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2], 'DIP_Loss': g[3]}
+                return g
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         recons_loss = F.mse_loss(recons, input, reduction='sum')
         kld_loss = torch.sum(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
@@ -638,9 +609,6 @@ class MIWAE(_HipVAE):
     def _loss_config(self) -> dict:
         return dict(loss="miwae", samples=self.num_samples, estimates=self.num_estimates)
 
-    def _dropin_config(self) -> dict:
-        return self._loss_config()
-
     def forward(self, input: Tensor, **kwargs) -> List[Tensor]:
         """miwae.py:124-130: [recons [B,M,K,C,H,W], input, mu [B,M,K,D], log_var [B,M,K,D], z, eps]."""
         B, M, K, D = input.shape[0], self.num_estimates, self.num_samples, self.latent_dim
@@ -651,7 +619,7 @@ class MIWAE(_HipVAE):
         z = eps_r * torch.exp(0.5 * lv_r) + mu_r
         eps_ret = (z - mu_r) / lv_r                         # miwae.py:129 (returned, unused by the loss)
         out = [recon.view(B, M, K, *recon.shape[1:]), input, mu_r, lv_r, z, eps_ret]
-        self._remember(out)
+        self._remember(out[:4], mu_r, lv_r)
         return out
 
     def decode(self, z: Tensor) -> Tensor:
@@ -665,19 +633,14 @@ class MIWAE(_HipVAE):
             key = ("rows", rows, self.training)
             if key not in self._plans:
                 self._plans[key] = StepPlan(self.net, rows, loss="vanilla", fused_loss=False, training=self.training)
-            plan, st = self._plans[key], L.stream_ptr()
-            self.net.sync_lowp()
-            plan.z.copy_(z.detach().reshape(plan.z.shape))
-            L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-            plan.decode(st)
-            recon = plan.recon.clone()
+            recon = self._decode(z, self._plans[key])
         return recon.view(*lead, *recon.shape[1:])
 
     def loss_function(self, *args, **kwargs) -> dict:
         """miwae.py:132-164."""
-        g = self._gpu_loss(args, "miwae", kld_weight=kwargs['M_N'])
+        g = self._gpu_loss(args, kld_weight=kwargs['M_N'])
         if g is not None:
-            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': g[2]}
+            return g
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         input = input.repeat(self.num_estimates, self.num_samples, 1, 1, 1, 1).permute(2, 0, 1, 3, 4, 5)
         kld_weight = kwargs['M_N']
@@ -849,6 +812,9 @@ class Autoencoder(_HipVAE):
     def _loss_config(self) -> dict:
         return dict(loss="vanilla", samples=1, recon_loss=self._recon_loss_cfg(self.net.device))
 
+    def _dropin_config(self) -> dict:
+        return _HipVAE._loss_config(self)       # (the other reconstruction losses run in loss_function)
+
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
                          plan_options: Optional[dict] = None):
@@ -871,21 +837,16 @@ class Autoencoder(_HipVAE):
         recon, z, lv, _ = self._run(input, torch.zeros(B, self.latent_dim, device=input.device))
         zeros = torch.zeros(B, self.latent_dim, device=input.device)
         out = [recon, input, zeros, zeros.clone()]
-        if self.training and torch.is_grad_enabled() and recon.grad_fn is not None:
-            self._last = (self._plan(B), input, recon, z, lv)
-        else:
-            self._last = None
+        self._remember(out[:2], z, lv)          # (the hidden z = fc(h) and the zero log-variance behind it)
         return out
 
     def loss_function(self, *args, **kwargs) -> dict:
         """autoencoder.py:230-262."""
         recons, input = args[0], args[1]
         zero = torch.tensor(0.0, device=recons.device)
-        last = self._last
-        if (self.center_focus_sigma is None and self.mssim is None and last is not None and self.training
-                and torch.is_grad_enabled() and recons is last[2] and input is last[1]):
-            g = _HipELBO.apply(self.flat, last[2], last[3], last[4], last[0], dict(loss="vanilla", kld_weight=0.0))
-            return {'loss': g[0], 'Reconstruction_Loss': g[1], 'KLD': zero, 'feature_loss': zero}
+        g = self._gpu_loss(args, kld_weight=0.0) if self.center_focus_sigma is None and self.mssim is None else None
+        if g is not None:
+            return {**g, 'KLD': zero, 'feature_loss': zero}
         cfg = (self._recon_loss_cfg(recons.device) if recons.is_cuda and recons.dim() == 4
                and recons.shape[2] * recons.shape[3] <= 4096 and recons.shape[2:] == input.shape[2:] else None)
         if cfg is not None and cfg["kind"] == "mssim":
@@ -932,11 +893,7 @@ class _VQStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat: Tensor, x: Tensor, model: "VQVAE"):
         plan = model._plan(x.shape[0])
-        st = L.stream_ptr()
-        model.net.sync_lowp()
-        plan.x.copy_(x.detach().to(plan.x.dtype))
-        L.call("vae_step_begin", plan.zero.data_ptr(), plan.zero.numel() * 4, plan.step.data_ptr(), st)
-        plan.forward(st)
+        _run_forward(plan, plan.fwd_calls, x=x)
         ctx.plan = plan
         n = plan.q.numel()
         vq_loss = plan.vq_sse[0] * ((1.0 + plan.beta) / n)      # commitment*beta + embedding (:47-50)
@@ -990,21 +947,13 @@ class VQVAE(BaseVAE):
     def encode(self, input: Tensor) -> List[Tensor]:
         """vq_vae.py:168-176: the encoder output (after its final LeakyReLU), NCHW."""
         plan = self._plan(input.shape[0])
-        st = L.stream_ptr()
-        self.net.sync_lowp()
-        plan.x.copy_(input.detach())
-        plan.begin(st)
-        plan._run(plan.fwd_calls[:plan.n_encode], st)
+        _run_forward(plan, plan.fwd_calls[:plan.n_encode], x=input)
         return [F.leaky_relu(plan.latpre.float(), 0.01).permute(0, 3, 1, 2).contiguous()]
 
     def decode(self, z: Tensor) -> Tensor:
         """vq_vae.py:178-187: decoder on (quantized) latents [B x D x H x W]."""
         plan = self._plan(z.shape[0])
-        st = L.stream_ptr()
-        self.net.sync_lowp()
-        plan.q.copy_(z.detach().permute(0, 2, 3, 1))
-        plan.begin(st)
-        plan._run(plan.fwd_calls[plan.n_decode0:plan.n_decode1], st)
+        _run_forward(plan, plan.fwd_calls[plan.n_decode0:plan.n_decode1], q=z.permute(0, 2, 3, 1))
         return plan.recon.clone()
 
     def forward(self, input: Tensor, **kwargs) -> List[Tensor]:

@@ -24,6 +24,7 @@ from . import _lib as L
 from .calls import BATCH_FN, batch_filter_calls, call_one, run_calls, size_workspaces, structs  # noqa: F401
 from .layout import reference_key_order, vanilla_layout
 from .plan import NetBase, PlanBase, ZeroRegion, _pad4, make_swaps                              # noqa: F401
+from .terms import MMD_KINDS, TERMS
 
 SLOPE = 0.01         # nn.LeakyReLU default
 # layers at least this large take materialised operands by default (StepPlan.big_layer,
@@ -79,6 +80,7 @@ class StepPlan(PlanBase):
     latent_var; its MMD term runs on vae_mmd_fwd right after the reparameterization.
     'dip' (DIP-VAE, models/dip_vae.py:125-164) takes lambda_diag and lambda_offdiag; its covariance
     penalty runs on vae_dip_fwd as soon as mu | log_var are final.
+    Such a batch-coupled latent term is `self.term` (terms.py) of a training plan, None otherwise.
     grads land in `self.grads` (same layout as net.params); `zero` (grads, BN sums, SSE,
     d[mu|logvar]) is cleared by `vae_step_begin` at the start of every step."""
 
@@ -141,13 +143,11 @@ class StepPlan(PlanBase):
         self.kld_weight, self.beta, self.gamma = kld_weight, beta, gamma
         if kernel_type not in MMD_KINDS:
             raise ValueError('Undefined kernel type.')                   # info_vae.py:173
-        if loss in ("info", "dip") and fused_loss and not training:
+        if loss in TERMS and fused_loss and not training:
             # an eval plan has no MMD / DIP call (nothing to seed), so the fused ELBO would find no
             # partials: the loss of an eval forward is the caller's (models.InfoVAE, models.DIPVAE)
             raise ValueError(f"StepPlan(loss='{loss}', training=False) has no fused loss: pass fused_loss=False")
-        self.lambda_diag, self.lambda_offdiag = lambda_diag, lambda_offdiag
-        self.alpha, self.reg_weight, self.kernel_type, self.latent_var = alpha, reg_weight, kernel_type, latent_var
-        self.c_max, self.c_stop = max_capacity, capacity_max_iter
+        self.max_capacity, self.capacity_max_iter = max_capacity, capacity_max_iter
         dev, T = net.device, net.dtype
         D, h, img = net.latent_dim, net.hidden_dims, net.img_size
         B, BS = self.B, self.B * self.S
@@ -198,20 +198,6 @@ class StepPlan(PlanBase):
         self.out = torch.zeros(4, **f32)                                  # loss, recon, KLD(report), kld
         self.per_img, self.head_coef, self.kl_coef = (torch.zeros(BS, **f32) for _ in range(3))
         self.num_iter = torch.zeros(1, **f32)                             # BetaVAE-B counter (beta_vae.py:132)
-        # InfoVAE's MMD term (vae_mmd_fwd): the prior sample (an input, or drawn on the device:
-        # use_device_prior), dmmd/dz, the mmd value (vae_elbo_fwd's mmd_out) and the tile partials
-        self.prior = self.dz_mmd = self.mmd = self.mmd_ws = None
-        if self.loss_kind == L.LOSS_INFO and training:
-            self.prior = torch.zeros(B, D, **f32)
-            self.dz_mmd = torch.zeros(B, D, **f32)
-            self.mmd = torch.zeros(1, **f32)
-            self._mmd_scale = torch.zeros(1, **f32)                       # drop-in backward: dL/dloss * mmd_coef
-        # DIP-VAE's covariance penalty (vae_dip_fwd): its gradient d dip/d[mu | log_var], the dip value
-        # (vae_elbo_fwd writes it) and the workspace of tile partials
-        self.dmulv_dip = self.dip = self.dip_ws = None
-        if self.loss_kind == L.LOSS_DIP and training:
-            self.dmulv_dip = torch.zeros(B, 2 * D, **f32)
-            self.dip = torch.zeros(1, **f32)
         # backward buffers (gradients w.r.t. pre-activation of each stored tensor)
         self.g_enc = [torch.empty_like(t) for t in self.enc]
         self.g_h0 = torch.empty_like(self.h0)
@@ -262,6 +248,12 @@ class StepPlan(PlanBase):
         self.side_all = self.side is not None            # concurrent: every weight-gradient call
         if self.wg_overlap:
             self.side = torch.cuda.Stream(device=dev)
+        # the loss's batch-coupled latent term (InfoVAE's MMD, DIP-VAE's covariance penalty), with
+        # its buffers and its call; an eval plan has none (nothing to seed)
+        self.term = None
+        if loss in TERMS and training:
+            self.term = TERMS[loss](self, alpha=alpha, reg_weight=reg_weight, kernel_type=kernel_type,
+                                    latent_var=latent_var, lambda_diag=lambda_diag, lambda_offdiag=lambda_offdiag)
         self._build()
         if fuse_bn and training:
             # each BatchNorm finalisation carried by the call that produces its statistics
@@ -525,8 +517,8 @@ class StepPlan(PlanBase):
             self._add(F, "vae_latent_fc_fwd", la)
             self.n_encode = self.n_decode0 = len(F)     # (decode() of a fused plan starts at the reparameterization)
             F.append(("vae_latent_dec_fwd", F[-1][1]))
-            self._add_mmd(F)                   # (behind the kernel that draws / reads this step's eps)
-            self._add_dip(F)
+            if self.term is not None:          # (behind the kernel that draws / reads this step's eps)
+                self.term.queue(F)
             return
         a = L.LinearArgs(dtype=T, m=B, n=2 * D, k=4 * C5)
         a.x, a.x_xf = last.data_ptr(), self.bn_xf(pre, L.X_BN_ACT, _cnt(last), running=True)
@@ -535,8 +527,8 @@ class StepPlan(PlanBase):
         self._add(F, "vae_linear_fwd", a)
         self.n_encode = len(F)             # calls of encode(): encoder + fc_mu|fc_var
         F.append(("vae_reparam_fwd", (T, BS, self.S, D, self.mulv.data_ptr(), self.eps.data_ptr(), self.z.data_ptr())))
-        self._add_mmd(F)
-        self._add_dip(F)
+        if self.term is not None:
+            self.term.queue(F)
         self.n_decode0 = len(F)            # decode(): decoder_input .. head
         a = L.LinearArgs(dtype=T, m=BS, n=4 * r0, k=D)
         a.x, a.y = self.z.data_ptr(), self.h0.data_ptr()
@@ -589,16 +581,13 @@ class StepPlan(PlanBase):
             hd.sse = self.sse.data_ptr()
             self._add(F, "vae_head_fwd", hd)
         e = L.ElboArgs(kind=self.loss_kind, batch=B, samples=self.S, latent=self.net.latent_dim, img_elems=3 * img * img,
-                       kld_weight=self.kld_weight, beta=self.beta, gamma=self.gamma, c_max=self.c_max,
-                       c_stop_iter=self.c_stop)
+                       kld_weight=self.kld_weight, beta=self.beta, gamma=self.gamma, c_max=self.max_capacity,
+                       c_stop_iter=self.capacity_max_iter)
         e.iter, e.mulv, e.sse = self.num_iter.data_ptr(), self.mulv.data_ptr(), self.sse.data_ptr()
         e.out, e.per_img = self.out.data_ptr(), self.per_img.data_ptr()
         e.head_coef, e.kl_coef = self.head_coef.data_ptr(), self.kl_coef.data_ptr()
-        if self.mmd_ws is not None:
-            self._info_coefs(e, self.beta, self.alpha, self.reg_weight)
-            e.mmd_tiles, e.mmd_partials, e.mmd_out = self._mmd_tiles, self.mmd_ws.data_ptr(), self.mmd.data_ptr()
-        if self.dip_ws is not None:        # (VAE_LOSS_DIP reads its partials through the same three fields)
-            e.mmd_tiles, e.mmd_partials, e.mmd_out = self._dip_tiles, self.dip_ws.data_ptr(), self.dip.data_ptr()
+        if self.term is not None:
+            self.term.fill_elbo(e)
         if self.loss_kind == L.LOSS_MIWAE:  # (VAE_LOSS_MIWAE: the tile count is its estimates M)
             e.mmd_tiles = self.M
         self.n_decode1, self.elbo_args = len(F), e
@@ -734,55 +723,6 @@ class StepPlan(PlanBase):
                 self.bwd_sums(a, enc_pre[i - 1])
                 self._add(Bw, "vae_conv2d_bwd_data", a)
 
-    def _info_coefs(self, e, beta: float, alpha: float, reg_weight: float) -> float:
-        """The weights of info_vae.py:145-147 in vae_elbo_args; returns the MMD coefficient."""
-        e.recon_weight, e.kl_factor = beta, 1.0 - alpha
-        e.mmd_coef = (alpha + reg_weight - 1.0) / (self.B * (self.B - 1))
-        return e.mmd_coef
-
-    def _add_mmd(self, F):
-        """InfoVAE: the MMD of this step's latents (recomputed in fp32 from mu | log_var and eps)
-        against the prior sample, right behind the reparameterization.  In a fused-loss plan the call
-        is part of the forward and adds its share of d[mu|log_var] itself (its coefficient is a
-        constant of the plan); in a drop-in plan it runs at loss_function time (run_elbo) with
-        grad_scale 1 and the backward applies the stored dz scaled by dL/dloss (seed_mmd)."""
-        if self.loss_kind != L.LOSS_INFO or not self.training:
-            return
-        B, D = self.B, self.net.latent_dim
-        a = self._mmd = L.MmdArgs(kind=MMD_KINDS[self.kernel_type], batch=B, latent=D, latent_var=self.latent_var)
-        a.mulv, a.eps, a.prior, a.dz = (self.mulv.data_ptr(), self.eps.data_ptr(), self.prior.data_ptr(),
-                                        self.dz_mmd.data_ptr())
-        nbytes, self._mmd_tiles = L.mmd_workspace(a)
-        self.mmd_ws = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.net.device)
-        a.workspace, a.workspace_bytes = self.mmd_ws.data_ptr(), nbytes
-        if self.fused_loss:
-            a.grad_scale = (self.alpha + self.reg_weight - 1.0) / (B * (B - 1))
-            a.dmulv = self.dmulv.data_ptr()
-            self._add(F, "vae_mmd_fwd", a)
-        else:
-            a.grad_scale = 1.0
-            self._keep.append(a)
-
-    def _add_dip(self, F):
-        """DIP-VAE: the covariance penalty of this step's latent means and its gradient (vae_dip_fwd),
-        as soon as mu | log_var are final; it needs neither eps nor z.  In a fused-loss plan the call is
-        part of the forward and adds d dip/d[mu | log_var] into dmulv itself (the term's weight in the
-        loss is 1); in a drop-in plan it runs at loss_function time (run_elbo) and the backward applies
-        the stored gradient scaled by dL/dloss (seed_dip)."""
-        if self.loss_kind != L.LOSS_DIP or not self.training:
-            return
-        a = self._dip = L.DipArgs(batch=self.B, latent=self.net.latent_dim, lambda_diag=self.lambda_diag,
-                                  lambda_offdiag=self.lambda_offdiag, grad_scale=1.0)
-        a.mulv, a.dmulv_dip = self.mulv.data_ptr(), self.dmulv_dip.data_ptr()
-        nbytes, self._dip_tiles = L.dip_workspace(a)
-        self.dip_ws = torch.zeros(nbytes // 8 + 1, dtype=torch.float64, device=self.net.device)
-        a.workspace, a.workspace_bytes = self.dip_ws.data_ptr(), self.dip_ws.numel() * 8
-        if self.fused_loss:
-            a.dmulv = self.dmulv.data_ptr()
-            self._add(F, "vae_dip_fwd", a)
-        else:
-            self._keep.append(a)
-
     def _add_recon_loss(self, F):
         """The recon_loss call closing the forward (vae_recon_loss): loss terms into `out`, per-image
         MSE from the head's SSE, and dL/drecon into grad_recon for the backward."""
@@ -819,7 +759,8 @@ class StepPlan(PlanBase):
         if self.fused_loss and self.training and self.recon_loss is None:
             # (DIP-VAE's reconstruction term is the sum, dip_vae.py:141: no 1/(B*3*H*W))
             rc.dy = self.g8.data_ptr()
-            rc.grad_scale = 1.0 if self.loss_kind == L.LOSS_DIP else 1.0 / (self.B * 3 * img * img)
+            recon_sum = self.term is not None and self.term.recon_sum
+            rc.grad_scale = 1.0 if recon_sum else 1.0 / (self.B * 3 * img * img)
         self._add(F, "vae_recon_fwd", rc)
 
     def _wide_head_bwd(self, Bw):
@@ -860,16 +801,13 @@ class StepPlan(PlanBase):
         return True
 
     def use_device_prior(self, step: torch.Tensor, seed: int = 1265) -> bool:
-        """InfoVAE: draw the prior sample of compute_mmd (torch.randn_like(z), info_vae.py:220) on the
-        device inside vae_mmd_fwd, every step: the generator of use_device_eps on another stream word,
-        keyed by `seed` and the device step counter `step`; the draw is written to self.prior.  Works on
-        both bottleneck routes; returns False for a plan without an MMD term."""
-        if self.mmd_ws is None:
-            return False
-        a = self._mmd
-        a.prior_gen, a.prior_step, a.prior_seed = 1, step.data_ptr(), seed & 0xFFFFFFFFFFFFFFFF
-        self._prior_step = step
-        return True
+        """Have the latent term draw its prior sample (self.prior) on the device, every step
+        (MmdTerm.use_device_prior); returns False for a plan whose loss has no such input."""
+        return self.prior is not None and self.term.use_device_prior(step, seed)
+
+    @property
+    def prior(self):
+        return self.term.prior if self.term is not None else None
 
     def draw_noise(self, eps: bool = True, prior: bool = True):
         if eps:
@@ -883,34 +821,25 @@ class StepPlan(PlanBase):
         if self.loss_kind == L.LOSS_BETA_B:
             self.num_iter.add_(1.0)
 
-    def encode(self, stream=None):
-        """encoder + fc_mu|fc_var only (mu | log_var land in self.mulv)."""
-        self._run(self.fwd_calls[:self.n_encode], stream if stream is not None else L.stream_ptr())
-
-    def decode(self, stream=None):
-        """decoder_input .. head from self.z (reconstruction lands in self.recon)."""
-        self._run(self.fwd_calls[self.n_decode0:self.n_decode1], stream if stream is not None else L.stream_ptr())
-
     def loss_dict(self) -> Dict[str, float]:
         if self._loss_pending:
             raise RuntimeError("loss_dict(): this plan evaluates the ELBO in the head backward "
                                "(elbo_in_head); run backward() first")
         d = super().loss_dict()
-        if self.loss_kind == L.LOSS_INFO:       # info_vae.py:148: MMD before KLD
-            d["MMD"], d["KLD"] = float(self.mmd), d.pop("KLD")
-        elif self.loss_kind == L.LOSS_DIP:      # dip_vae.py:161-164: DIP_Loss last
-            d["DIP_Loss"] = float(self.dip)
+        if self.term is not None:
+            self.term.place(d, float(self.term.value))
         return d
 
     @property
     def extra_term(self):
         """(name, one-element tensor) of the loss dict's fourth entry, for the losses with a
         batch-coupled latent term (InfoVAE's MMD, DIP-VAE's DIP_Loss); None otherwise."""
-        if self.mmd is not None:
-            return "MMD", self.mmd
-        if self.dip is not None:
-            return "DIP_Loss", self.dip
-        return None
+        return (self.term.name, self.term.value) if self.term is not None else None
+
+    # the earlier spellings of the term's buffers, which the step tests read: the MMD's dmmd/dz and
+    # DIP-VAE's d dip/d[mu | log_var] (term.grad), the dip value (term.value; None without a term)
+    dz_mmd = dmulv_dip = property(lambda self: self.term.grad)
+    dip = property(lambda self: self.term.value if self.term is not None else None)
 
     # ------------------------------------------------------------------ drop-in ELBO
     # A drop-in plan (fused_loss=False) can still take its loss on the GPU: the BaseVAE
@@ -921,11 +850,13 @@ class StepPlan(PlanBase):
                   "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO, "dip": L.LOSS_DIP, "miwae": L.LOSS_MIWAE}
 
     def run_elbo(self, stream, loss: str, kld_weight: float, beta: float = 4.0, gamma: float = 1000.0,
-                 c_max: float = 25.0, c_stop_iter: float = 1e5, num_iter: Optional[int] = None,
-                 alpha: float = -0.5, reg_weight: float = 100.0, prior: Optional[torch.Tensor] = None):
+                 max_capacity: float = 25.0, capacity_max_iter: float = 1e5, num_iter: Optional[int] = None,
+                 alpha: float = -0.5, reg_weight: float = 100.0, prior: Optional[torch.Tensor] = None,
+                 c_max: Optional[float] = None, c_stop_iter: Optional[float] = None):
         """vae_elbo_fwd over this step's SSE and mu|log_var: out = [loss, Reconstruction_Loss, KLD
         as the reference reports it, raw KLD]; per_img; head_coef / kl_coef = dloss/dsse_i and the
-        per-row KL gradient coefficient (the backward seeds)."""
+        per-row KL gradient coefficient (the backward seeds).  The loss arguments are spelled as the
+        constructor's; c_max / c_stop_iter are the older names of max_capacity / capacity_max_iter."""
         e = self.elbo_args
         e.kind = self.LOSS_KINDS[loss]
         if e.kind == L.LOSS_MIWAE:
@@ -935,38 +866,17 @@ class StepPlan(PlanBase):
             e.mmd_tiles = self.M
         elif (e.kind == L.LOSS_IWAE) != (self.S > 1):
             raise ValueError(f"loss {loss!r} on a plan with {self.S} samples per image")
-        e.kld_weight, e.beta, e.gamma, e.c_max, e.c_stop_iter = kld_weight, beta, gamma, c_max, c_stop_iter
+        e.kld_weight, e.beta, e.gamma = kld_weight, beta, gamma
+        e.c_max = max_capacity if c_max is None else c_max
+        e.c_stop_iter = capacity_max_iter if c_stop_iter is None else c_stop_iter
         if num_iter is not None:
             self.num_iter.fill_(float(num_iter))
-        if e.kind == L.LOSS_INFO:
-            # the MMD of this forward's latents into dz_mmd (unscaled) and the partials the loss adds
-            if self.mmd_ws is None or self.fused_loss:
-                raise ValueError("run_elbo('info') needs a drop-in plan built with loss='info'")
-            if prior is not None:
-                self.prior.copy_(prior.detach().reshape(self.prior.shape))
-            self.mmd_coef = self._info_coefs(e, beta, alpha, reg_weight)
-            L.call("vae_mmd_fwd", self._mmd, stream)
-        if e.kind == L.LOSS_DIP:
-            # the penalty of this forward's means: its unscaled gradient into dmulv_dip, the partials the
-            # loss adds into the workspace (the lambdas are the plan's)
-            if self.dip_ws is None or self.fused_loss:
-                raise ValueError("run_elbo('dip') needs a drop-in plan built with loss='dip'")
-            L.call("vae_dip_fwd", self._dip, stream)
+        if loss in TERMS:
+            # the term of this forward's latents: its unscaled gradient and the partials the loss adds
+            if not isinstance(self.term, TERMS[loss]) or self.fused_loss:
+                raise ValueError(f"run_elbo({loss!r}) needs a drop-in plan built with loss={loss!r}")
+            self.term.run(e, stream, beta=beta, alpha=alpha, reg_weight=reg_weight, prior=prior)
         L.call("vae_elbo_fwd", e, stream)
-
-    def seed_dip(self, g_loss: torch.Tensor, seed: torch.Tensor):
-        """Drop-in backward of the DIP term: dmulv += dL/dloss * seed, the d dip/d[mu | log_var] that
-        vae_dip_fwd stored at run_elbo, next to the two seeds seed_fused switches on.  dmulv is zero
-        here (the step head or reset_backward) and the backward accumulates onto it."""
-        self.dmulv.view(seed.shape).addcmul_(seed, g_loss.reshape(1, 1).to(seed))
-
-    def seed_mmd(self, g_loss: torch.Tensor, mmd_coef: float, stream):
-        """Drop-in backward of the MMD term: dmulv += reparameterization backward of
-        (dL/dloss * mmd_coef) * dz_mmd (vae_mmd_reseed), next to the two seeds seed_fused switches on.
-        dmulv is zero here (the step head or reset_backward) and the backward accumulates onto it."""
-        torch.mul(g_loss.reshape(1).to(self._mmd_scale), mmd_coef, out=self._mmd_scale)
-        L.call("vae_mmd_reseed", self.B, self.net.latent_dim, self.dz_mmd.data_ptr(), self._mmd_scale.data_ptr(),
-               self.mulv.data_ptr(), self.eps.data_ptr(), self.dmulv.data_ptr(), stream)
 
     def seed_fused(self, on: bool):
         """Backward seeding of a drop-in plan: on — from head_coef / kl_coef (run_elbo); off — from
@@ -1001,9 +911,6 @@ class StepPlan(PlanBase):
         if self.wide_head:
             self.dw8h.zero_()
             self.db8h.zero_()
-
-
-MMD_KINDS = {"imq": L.MMD_IMQ, "rbf": L.MMD_RBF}
 
 
 def bn_reps(channels: int) -> int:

@@ -27,6 +27,8 @@ import json
 import os
 import sys
 
+import torch
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 AE_BIG = [128, 256, 512, 1024, 2048]
@@ -46,6 +48,16 @@ CONFIGS = {
     "vanilla_fp32_b4": ("vae", {}, 4, {}),
     "vq_b8": ("vq", {}, 8, {}),
     "vq_fp32_b8": ("vq", {}, 8, {}),
+    # the losses with a batch-coupled latent term (vae_amd/terms.py) and their neighbours
+    "dip_b16": ("vae", {}, 16, dict(loss="dip")),
+    "miwae_b4_m2k3": ("vae", {}, 4, dict(loss="miwae", samples=3, estimates=2)),
+    "betaB_b16": ("vae", {}, 16, dict(loss="betaB")),
+    "info_dropin_b4": ("vae", {}, 4, dict(loss="info", fused_loss=False)),
+    "dip_dropin_b4": ("vae", {}, 4, dict(loss="dip", fused_loss=False)),
+    "miwae_dropin_b2": ("vae", {}, 2, dict(loss="miwae", fused_loss=False, samples=2, estimates=2)),
+    "info_per_op_b16": ("vae", {}, 16, dict(loss="info", latent_kernels=False)),
+    "dip_fp32_b4": ("vae", {}, 4, dict(loss="dip")),
+    "center_b4": ("vae", {}, 4, dict(recon_loss={"kind": "center", "mask": torch.ones(64, 64)}, kld_weight=0.0)),
 }
 
 
@@ -67,7 +79,6 @@ def no_launches(L):
 
 def build(name, **override):
     """(net, plan) of a configuration on the CPU; `override` replaces plan arguments."""
-    import torch
     from vae_amd import _lib as L
     kind, net_kw, batch, plan_kw = CONFIGS[name]
     dtype = torch.float32 if "fp32" in name else torch.bfloat16
@@ -171,7 +182,6 @@ class Writer:
 
 def describe(name, **override):
     """The JSON-able description of one configuration (see the module docstring)."""
-    import torch
     from vae_amd import dp
     from vae_amd.engine import begin_args
     net, plan = build(name, **override)
