@@ -523,6 +523,29 @@ int vae_dip_workspace_size(const vae_dip_args* a, size_t* bytes, int32_t* tiles)
 int vae_adam_step(int64_t n, float* p, const float* g, float* m, float* v,
                   const int32_t* step, const float* lr, double beta1, double beta2, float eps,
                   float weight_decay, void* p_lowp, void* stream);
+/* --- Gradient-norm clipping (Lightning's trainer_params.gradient_clip_val:
+ *     torch.nn.utils.clip_grad_norm_(parameters, max_norm), L2 norm, error_if_nonfinite=False) as
+ *     two launches with no host round trip, so a captured step replays them.
+ * vae_grad_sumsq: the sum of g[i]^2 over the flat fp32 gradient as *nparts_out (host) <=
+ *   VAE_SUMSQ_MAX_PARTS double partial sums, one per workgroup.  Each workgroup covers a contiguous
+ *   range fixed by n alone and adds in a fixed order, products and sums in double, without atomics:
+ *   the partials are bit-identical at every run.  `partials` is a workspace of VAE_SUMSQ_MAX_PARTS
+ *   doubles (8-byte aligned) whatever n is.  16-byte loads when g is 16-byte aligned, else one
+ *   element per load.
+ * vae_adam_step_clip: vae_adam_step with every gradient element multiplied (one fp32 multiply,
+ *   before weight decay) by
+ *       coef = min(1, *max_norm / (total + 1e-6)),  total = (float)sqrt(sum of the partials),
+ *   which every workgroup derives from the partials in the same fixed order.  A NaN total gives a NaN
+ *   coefficient and an infinite one 0, as in torch.  g is only READ: the gradient buffer stays
+ *   UNCLIPPED in memory (nothing is written back to it); a caller that wants the clipped gradient
+ *   multiplies by norm_out[1].  norm_out[0] = total, norm_out[1] = coef (device, two floats).
+ *   max_norm is a device scalar like lr: it can change between replays of a captured step. --- */
+#define VAE_SUMSQ_MAX_PARTS 1024
+int vae_grad_sumsq(int64_t n, const float* g, double* partials, int32_t* nparts_out, void* stream);
+int vae_adam_step_clip(int64_t n, float* p, const float* g, float* m, float* v,
+                       const int32_t* step, const float* lr, double beta1, double beta2, float eps,
+                       float weight_decay, void* p_lowp, const double* partials, int32_t nparts,
+                       const float* max_norm, float* norm_out, void* stream);
 /* --- Deferred weight-gradient reductions + Adam in one launch ---------------------------
  * A bf16 call with defer_reduce set leaves a weight gradient as fp32 partial rows and records
  *   dst[j] = sum_{r < rows} slab[r * ld + j]   (j < count, rows summed in ascending order)

@@ -1,6 +1,8 @@
 // The optimizer step (torch.optim.Adam's single-tensor update) over the flat parameter buffer:
 // vae_adam_step, vae_adam_step_ex (the same update with the backward's deferred weight-gradient
-// reductions and loss in its grid) and vae_cast_bf16 (the bf16 parameter copy).
+// reductions and loss in its grid), vae_grad_sumsq + vae_adam_step_clip (the update under
+// clip_grad_norm_: the gradient's sum of squares, then Adam with the clip coefficient folded in) and
+// vae_cast_bf16 (the bf16 parameter copy).
 #include <algorithm>
 
 #include <math.h>
@@ -70,6 +72,132 @@ __global__ void __launch_bounds__(256) adam_kernel(long n, float* __restrict__ p
   }
 }
 
+// ---------------------------------------------------------------------------- gradient-norm clip
+// vae_grad_sumsq: workgroup b sums g[i]^2 over the contiguous range of quads (V = 4) or elements
+// (V = 1) that n and the grid alone assign to it — thread t takes t, t + 256, ... in ascending order,
+// products and sums in double (a product of two floats is exact in double) — then the 64 lanes of a
+// wave combine by shuffles and the four waves in LDS, in a fixed order: partials[b] is the same bits
+// at every run.  No atomics; the n % 4 tail goes to workgroup 0.
+constexpr int kSumsqPer = 4096;        // elements per workgroup before the grid reaches its cap
+inline int sumsq_parts(long n) {
+  const long b = (n + kSumsqPer - 1) / kSumsqPer;
+  return (int)std::min<long>(std::max<long>(b, 1), VAE_SUMSQ_MAX_PARTS);
+}
+template <int V>
+__global__ void __launch_bounds__(256) grad_sumsq_kernel(long n, const float* __restrict__ g,
+                                                         double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const long nv = n / V;
+  const long chunk = (nv + gridDim.x - 1) / gridDim.x;
+  const long lo = (long)blockIdx.x * chunk;
+  const long hi = lo + chunk < nv ? lo + chunk : nv;
+  double acc = 0.0;
+  auto add = [&](float x) { acc = fma((double)x, (double)x, acc); };
+  long i = lo + tid;
+  if constexpr (V == 4) {
+    // four 16-byte loads in flight per thread, added in the order they were issued
+    for (; i + 3 * 256 < hi; i += 4 * 256) {
+      f32x4 t[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) t[u] = reinterpret_cast<const f32x4*>(g)[i + 256 * u];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) add(t[u][e]);
+    }
+    for (; i < hi; i += 256) {
+      const f32x4 t = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) add(t[e]);
+    }
+    if (blockIdx.x == 0 && tid < n - nv * V) add(g[nv * V + tid]);
+  } else {
+    for (; i < hi; i += 256) add(g[i]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) partials[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// The clip coefficient of torch.nn.utils.clip_grad_norm_ (L2 norm, error_if_nonfinite=False) from
+// vae_grad_sumsq's partials, by all 256 threads of a workgroup: thread t adds partials t, t + 256,
+// ... in ascending order, an LDS tree adds the 256 sums — the same order in every workgroup, so all
+// of them hold the bit-identical total and coefficient.  A NaN norm gives a NaN coefficient and an
+// infinite one 0, as torch.clamp(max_norm / (total + 1e-6), max=1.0) does.
+__device__ __forceinline__ float clip_coef(const double* __restrict__ partials, int nparts, const float* max_norm,
+                                           float* norm_out) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  double s = 0.0;
+  for (int i = tid; i < nparts; i += 256) s += partials[i];
+  red[tid] = s;
+  __syncthreads();
+#pragma unroll
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  const float total = (float)sqrt(red[0]);
+  const float c = *max_norm / (total + 1e-6f);
+  const float coef = c > 1.f ? 1.f : c;
+  if (blockIdx.x == 0 && tid == 0) {
+    norm_out[0] = total;
+    norm_out[1] = coef;
+  }
+  return coef;
+}
+
+// adam_kernel with every gradient element multiplied by the clip coefficient first (one fp32
+// multiply, never contracted into the update; g is only read).  A sibling, not a template parameter
+// of adam_kernel: sharing the body through an inlined helper moved adam_kernel's register allocation,
+// and the unclipped kernel is on every benched path.
+template <bool LOWP, int V>
+__global__ void __launch_bounds__(256) adam_clip_kernel(long n, float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, float* __restrict__ v, const int* step,
+                                                        const float* lr, double b1, double b2, float eps, float wd,
+                                                        __bf16* __restrict__ lowp, const double* __restrict__ partials,
+                                                        int nparts, const float* max_norm, float* norm_out) {
+  const float coef = clip_coef(partials, nparts, max_norm, norm_out);
+  const double t = (double)(*step);
+  const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+  const AdamK k{(float)(1.0 - b1), (float)(1.0 - b2), (float)b2, (float)((double)*lr / bc1), (float)sqrt(bc2), eps, wd};
+  const long stride = (long)gridDim.x * blockDim.x;
+  const long nv = n / V;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+    if constexpr (V == 4) {
+      f32x4 p4 = reinterpret_cast<const f32x4*>(p)[i];
+      const f32x4 g4 = reinterpret_cast<const f32x4*>(g)[i];
+      f32x4 m4 = reinterpret_cast<const f32x4*>(m)[i];
+      f32x4 v4 = reinterpret_cast<const f32x4*>(v)[i];
+      float pe[4], me[4], ve[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        pe[e] = p4[e]; me[e] = m4[e]; ve[e] = v4[e];
+        adam_elem(k, pe[e], __fmul_rn(g4[e], coef), me[e], ve[e]);
+      }
+      reinterpret_cast<f32x4*>(p)[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
+      reinterpret_cast<f32x4*>(m)[i] = f32x4{me[0], me[1], me[2], me[3]};
+      reinterpret_cast<f32x4*>(v)[i] = f32x4{ve[0], ve[1], ve[2], ve[3]};
+      if (LOWP) reinterpret_cast<bf16x4*>(lowp)[i] = bf16x4{(__bf16)pe[0], (__bf16)pe[1], (__bf16)pe[2], (__bf16)pe[3]};
+    } else {
+      float pi = p[i], mi = m[i], vi = v[i];
+      adam_elem(k, pi, __fmul_rn(g[i], coef), mi, vi);
+      m[i] = mi; v[i] = vi; p[i] = pi;
+      if (LOWP) lowp[i] = (__bf16)pi;
+    }
+  }
+  if (V > 1 && blockIdx.x == 0 && threadIdx.x < n - nv * V) {
+    const long i = nv * V + threadIdx.x;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adam_elem(k, pi, __fmul_rn(g[i], coef), mi, vi);
+    m[i] = mi; v[i] = vi; p[i] = pi;
+    if (LOWP) lowp[i] = (__bf16)pi;
+  }
+}
+
 __global__ void cast_bf16_kernel(long n, const float* src, __bf16* dst) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     dst[i] = (__bf16)src[i];
@@ -99,6 +227,48 @@ extern "C" int vae_adam_step(int64_t n, float* p, const float* g, float* m, floa
     else VAE_LAUNCH((adam_kernel<false, 1>), dim3(grid), dim3(256), 0, st, (long)n, p, g, m, v, step, lr, beta1, beta2, eps, weight_decay, lp);
   }
   return check_launch("adam_step");
+}
+
+extern "C" int vae_grad_sumsq(int64_t n, const float* g, double* partials, int32_t* nparts_out, void* stream) {
+  if (!nparts_out) return fail(VAE_E_BADARG, "grad_sumsq: nparts_out");
+  *nparts_out = 0;
+  if (n <= 0) return VAE_OK;
+  if (!g || !partials) return fail(VAE_E_BADARG, "grad_sumsq: null");
+  if ((uintptr_t)partials % 8) return fail(VAE_E_BADARG, "grad_sumsq: partials must be 8-byte aligned");
+  const int parts = sumsq_parts(n);
+  const hipStream_t st = (hipStream_t)stream;
+  if ((uintptr_t)g % 16 == 0) VAE_LAUNCH(grad_sumsq_kernel<4>, dim3(parts), dim3(256), 0, st, (long)n, g, partials);
+  else VAE_LAUNCH(grad_sumsq_kernel<1>, dim3(parts), dim3(256), 0, st, (long)n, g, partials);
+  *nparts_out = parts;
+  return check_launch("grad_sumsq");
+}
+
+extern "C" int vae_adam_step_clip(int64_t n, float* p, const float* g, float* m, float* v, const int32_t* step,
+                                  const float* lr, double beta1, double beta2, float eps, float weight_decay,
+                                  void* p_lowp, const double* partials, int32_t nparts, const float* max_norm,
+                                  float* norm_out, void* stream) {
+  if (n <= 0) return VAE_OK;
+  if (!p || !g || !m || !v || !step || !lr || !partials || !max_norm || !norm_out)
+    return fail(VAE_E_BADARG, "adam_step_clip: null");
+  if (nparts < 1 || nparts > VAE_SUMSQ_MAX_PARTS) return fail(VAE_E_BADARG, "adam_step_clip: %d partials", nparts);
+  auto al = [](const void* q, uintptr_t a) { return ((uintptr_t)q % a) == 0; };
+  if (!al(partials, 8)) return fail(VAE_E_BADARG, "adam_step_clip: partials must be 8-byte aligned");
+  const bool vec = al(p, 16) && al(g, 16) && al(m, 16) && al(v, 16) && (!p_lowp || al(p_lowp, 8));
+  const hipStream_t st = (hipStream_t)stream;
+  __bf16* lp = (__bf16*)p_lowp;
+  const int grid = vec ? grid_for((n + 3) / 4) : grid_for(n);
+#define VAE_CLIP_LAUNCH(LOWP, V)                                                                                  \
+  VAE_LAUNCH((adam_clip_kernel<LOWP, V>), dim3(grid), dim3(256), 0, st, (long)n, p, g, m, v, step, lr, beta1, beta2, \
+             eps, weight_decay, lp, partials, (int)nparts, max_norm, norm_out)
+  if (vec) {
+    if (p_lowp) VAE_CLIP_LAUNCH(true, 4);
+    else VAE_CLIP_LAUNCH(false, 4);
+  } else {
+    if (p_lowp) VAE_CLIP_LAUNCH(true, 1);
+    else VAE_CLIP_LAUNCH(false, 1);
+  }
+#undef VAE_CLIP_LAUNCH
+  return check_launch("adam_step_clip");
 }
 
 namespace {

@@ -110,6 +110,7 @@ class DipArgs(ctypes.Structure):
 
 
 SLAB_MAX = 32                      # vaehip.h VAE_SLAB_MAX
+SUMSQ_MAX_PARTS = 1024             # vaehip.h VAE_SUMSQ_MAX_PARTS (vae_grad_sumsq's workspace, in doubles)
 
 
 class GradSlab(ctypes.Structure):
@@ -235,6 +236,10 @@ _SIGS = {
     "vae_recon_bwd": [POINTER(ReconArgs), c_void_p],
     "vae_adam_step": [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
                       ctypes.c_double, c_float, c_float, c_void_p, c_void_p],
+    "vae_grad_sumsq": [c_int64, c_void_p, c_void_p, POINTER(c_int32), c_void_p],
+    "vae_adam_step_clip": [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                           ctypes.c_double, c_float, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                           c_void_p],
     "vae_cast_bf16": [c_int64, c_void_p, c_void_p, c_void_p],
     "vae_deferred_reset": [],
     "vae_deferred_take": [POINTER(GradSlab), c_int32, POINTER(ElboArgs), POINTER(c_int32)],

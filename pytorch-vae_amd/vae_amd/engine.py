@@ -23,11 +23,20 @@ from .plan import DEFERRED_MSG, NetBase
 
 class FusedAdam:
     """torch.optim.Adam semantics (lerp first moment, bias-corrected) over the flat buffer;
-    also refreshes the bf16 weight copy in the same pass.  step and lr are device scalars."""
+    also refreshes the bf16 weight copy in the same pass.  step and lr are device scalars.
+
+    max_grad_norm (Lightning's gradient_clip_val: torch.nn.utils.clip_grad_norm_ before the step):
+    apply() runs vae_grad_sumsq, then vae_adam_step_clip with the clip coefficient folded into the
+    update.  The gradient buffer stays unclipped; `grad_norm` holds [norm, coef] of the last step."""
 
     def __init__(self, net: NetBase, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None):
+                 m: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                 max_grad_norm: Optional[float] = None):
         self.net = net
+        self.max_grad_norm = self.grad_norm = self._partials = None
+        self._nparts = ctypes.c_int32(0)
+        if max_grad_norm is not None:
+            self.set_max_grad_norm(max_grad_norm)
         # m / v may be given: a torch.optim.Adam's exp_avg / exp_avg_sq of the same flat
         # parameter, so that optimizer's state (checkpoints) IS this one (experiment.GraphedSteps)
         self.m = m if m is not None else torch.zeros_like(net.params)
@@ -39,12 +48,27 @@ class FusedAdam:
     def set_lr(self, lr: float):
         self.lr.fill_(float(lr))
 
+    def set_max_grad_norm(self, max_grad_norm: float):
+        """The clip threshold, a device scalar like lr (a captured step reads it at every replay)."""
+        if not float(max_grad_norm) > 0:
+            raise ValueError(f"max_grad_norm {max_grad_norm!r}: must be > 0 (None: no clipping)")
+        if self.max_grad_norm is None:
+            dev = self.net.device
+            self.max_grad_norm = torch.empty(1, dtype=torch.float32, device=dev)
+            self.grad_norm = torch.zeros(2, dtype=torch.float32, device=dev)
+            self._partials = torch.zeros(L.SUMSQ_MAX_PARTS, dtype=torch.float64, device=dev)
+        self.max_grad_norm.fill_(float(max_grad_norm))
+
     def apply_deferred(self, grads: torch.Tensor, slabs, elbo, stream=None, lo: int = 0, hi: Optional[int] = None):
         """apply() with the weight-gradient reductions the backward deferred (L.deferred_take) done in
         the same launch (vae_adam_step_ex): each reduced gradient is written into `grads` before its
         elements' update, and a deferred loss is evaluated by one extra workgroup.  [lo, hi): the
         elements this launch updates (a multiple of 4 apart from 0; the descriptors must lie inside)."""
         net = self.net
+        if self.max_grad_norm is not None:
+            raise RuntimeError("FusedAdam(max_grad_norm=...): the gradient must be complete before its norm is "
+                               "taken, so the deferred reductions of vae_adam_step_ex cannot run under clipping; "
+                               "use apply() on a step built with defer_reductions=False")
         if len(slabs) > L.SLAB_MAX:
             raise ValueError(f"{len(slabs)} deferred reductions > {L.SLAB_MAX}")
         hi = net.params.numel() if hi is None else hi
@@ -70,10 +94,16 @@ class FusedAdam:
         the swapped-axes weight copies stale (net.swaps_stale) for a caller that refreshes them at the
         start of its next step (TrainStep: inside vae_step_begin_ex)."""
         net = self.net
-        L.call("vae_adam_step", net.params.numel(), net.params.data_ptr(), grads.data_ptr(), self.m.data_ptr(),
-               self.v.data_ptr(), self.step.data_ptr(), self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
-               self.weight_decay, net.lowp.data_ptr() if net.lowp is not None else None,
-               stream if stream is not None else L.stream_ptr())
+        st = stream if stream is not None else L.stream_ptr()
+        adam = (net.params.numel(), net.params.data_ptr(), grads.data_ptr(), self.m.data_ptr(),
+                self.v.data_ptr(), self.step.data_ptr(), self.lr.data_ptr(), self.betas[0], self.betas[1], self.eps,
+                self.weight_decay, net.lowp.data_ptr() if net.lowp is not None else None)
+        if self.max_grad_norm is None:
+            L.call("vae_adam_step", *adam, st)
+        else:
+            L.call("vae_grad_sumsq", adam[0], adam[2], self._partials.data_ptr(), ctypes.byref(self._nparts), st)
+            L.call("vae_adam_step_clip", *adam, self._partials.data_ptr(), self._nparts.value,
+                   self.max_grad_norm.data_ptr(), self.grad_norm.data_ptr(), st)
         if net.swap_descs:
             if refresh_swaps:
                 net.refresh_swaps(stream)
@@ -145,8 +175,11 @@ class TrainStep:
         # one rank: the backward's weight-gradient slab reductions (and the loss fused into the head
         # backward) run inside the optimizer launch (StepPlan.defer_reductions, vae_adam_step_ex);
         # with more ranks the gradients must be complete before their all-reduce — which a plan that
-        # another step has deferred cannot give any more
-        will_defer = defer_reductions and not exchange
+        # another step has deferred cannot give any more.  Likewise under gradient clipping
+        # (FusedAdam(max_grad_norm=...)): the norm is taken over the complete gradient — after the last
+        # bucket's all-reduce has joined, so over the rank mean and the same on every rank — by
+        # FusedAdam.apply, which runs vae_grad_sumsq and vae_adam_step_clip in place of vae_adam_step
+        will_defer = defer_reductions and not exchange and opt.max_grad_norm is None
         if plan.deferred and not will_defer:
             raise RuntimeError(DEFERRED_MSG)
         if exchange:

@@ -215,10 +215,14 @@ class GraphedSteps:
 
     No host synchronisation per step: the loss terms stay device tensors in experiment.logged;
     per-image MSE and the extreme-image candidates are kept on the device and handed to the data
-    module / experiment.extreme_images by flush() (fit() calls it once per epoch)."""
+    module / experiment.extreme_images by flush() (fit() calls it once per epoch).
 
-    def __init__(self, experiment: VAEXperiment, optimizer):
+    gradient_clip_val (the reference's trainer_params.gradient_clip_val, Lightning's
+    clip_grad_norm_ between backward and optimizer.step): the shared FusedAdam's max_grad_norm."""
+
+    def __init__(self, experiment: VAEXperiment, optimizer, gradient_clip_val: Optional[float] = None):
         self.exp, self.opt = experiment, optimizer
+        self.gradient_clip_val = gradient_clip_val or None           # (Lightning: 0 / None = no clipping)
         self.steps: Dict[int, Any] = {}
         p = experiment.params
         g = optimizer.param_groups[0]
@@ -246,7 +250,7 @@ class GraphedSteps:
             st['exp_avg'] = torch.zeros_like(flat, memory_format=torch.preserve_format)
             st['exp_avg_sq'] = torch.zeros_like(flat, memory_format=torch.preserve_format)
         fused = FusedAdam(model.net, lr=g['lr'], betas=g['betas'], eps=g['eps'], weight_decay=g['weight_decay'],
-                          m=st['exp_avg'].data, v=st['exp_avg_sq'].data)
+                          m=st['exp_avg'].data, v=st['exp_avg_sq'].data, max_grad_norm=self.gradient_clip_val)
         self.nstep = int(float(st['step']))
         fused.step.fill_(self.nstep)
         return fused
@@ -371,13 +375,17 @@ def _owns_flat(opt, model) -> bool:
 
 
 def fit(experiment: VAEXperiment, train_batches, epochs: int = 1, val_batches=None,
-        engine: str = "graph") -> List[Dict[str, float]]:
+        engine: str = "graph", gradient_clip_val: Optional[float] = None) -> List[Dict[str, float]]:
     """Minimal Trainer loop over an iterable of (imgs, labels, names) batches: the reference's
     Lightning fit() for one optimizer (zero_grad, training_step, backward, step, epoch-interval
     schedulers).  Returns the per-epoch mean of each logged term (host values, synced once per
     epoch).  engine="graph" (default): each training step is one GraphedSteps replay (models with
     fused_train_step; plain Adam on model.parameters()); models without it (or several optimizers)
-    run the eager path.  engine="eager": training_step + loss.backward() + optimizer.step()."""
+    run the eager path.  engine="eager": training_step + loss.backward() + optimizer.step().
+    gradient_clip_val: Lightning's trainer_params.gradient_clip_val — the global L2 norm of the
+    gradients clipped to it before every optimizer step (torch.nn.utils.clip_grad_norm_ on the eager
+    path, inside the fused step on the graph path); None or 0: no clipping."""
+    gradient_clip_val = gradient_clip_val or None
     opt_cfg = experiment.configure_optimizers()
     sched, plateau = [], None
     if isinstance(opt_cfg, dict):
@@ -393,7 +401,7 @@ def fit(experiment: VAEXperiment, train_batches, epochs: int = 1, val_batches=No
         # (configure_optimizers' own); any other setup keeps the eager path instead of raising
         if (hasattr(experiment.model, "fused_train_step") and len(optims) == 1 and _fusable(experiment.model)
                 and _owns_flat(optims[0], experiment.model)):
-            graphed = GraphedSteps(experiment, optims[0])
+            graphed = GraphedSteps(experiment, optims[0], gradient_clip_val)
     elif engine != "eager":
         raise ValueError(f"engine {engine!r}")
     history = []
@@ -414,6 +422,8 @@ def fit(experiment: VAEXperiment, train_batches, epochs: int = 1, val_batches=No
                 o.zero_grad(set_to_none=True)
             loss = experiment.training_step(batch, i)
             loss.backward()
+            if gradient_clip_val is not None:
+                torch.nn.utils.clip_grad_norm_(experiment.model.parameters(), gradient_clip_val)
             optims[0].step()
             acc()
         if graphed is not None:

@@ -254,7 +254,7 @@ class _HipVAE(BaseVAE):
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
                          plan_options: Optional[dict] = None, device_eps: Optional[int] = None,
-                         device_prior: Optional[int] = None):
+                         device_prior: Optional[int] = None, max_grad_norm: Optional[float] = None):
         """The whole training step of this model — forward, loss_function (vae_elbo_fwd), backward,
         [gradient all-reduce], Adam — as one engine.TrainStep on the model's own parameters,
         replayed from HIP graphs: the graph path of VAEXperiment.training_step + backward +
@@ -262,11 +262,15 @@ class _HipVAE(BaseVAE):
         (one Adam state for the steps of every batch size, as the reference's single optimizer).
         `plan_options`: StepPlan route options (latent_kernels, head_kernels, pad_rgb, materialise,
         mat_min_flops, batch_wgrads, wg_overlap).  `device_eps` / `device_prior`: seeds to draw eps (and
-        InfoVAE's prior sample) on the device inside the step (TrainStep)."""
+        InfoVAE's prior sample) on the device inside the step (TrainStep).  `max_grad_norm`: the
+        reference trainer's gradient_clip_val (clip_grad_norm_ between backward and the optimizer step),
+        set on the optimizer — FusedAdam(max_grad_norm=...), also a shared `opt`."""
         from .engine import FusedAdam, TrainStep
         plan = StepPlan(self.net, batch, kld_weight=kld_weight, **self._loss_config(), **(plan_options or {}))
         if opt is None:
-            opt = FusedAdam(self.net, lr=lr, betas=betas, weight_decay=weight_decay)
+            opt = FusedAdam(self.net, lr=lr, betas=betas, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        elif max_grad_norm is not None:
+            opt.set_max_grad_norm(max_grad_norm)
         return TrainStep(self.net, plan, opt, graph=graph, process_group=process_group, device_eps=device_eps,
                          device_prior=device_prior)
 
@@ -817,12 +821,12 @@ class Autoencoder(_HipVAE):
 
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
-                         plan_options: Optional[dict] = None):
+                         plan_options: Optional[dict] = None, max_grad_norm: Optional[float] = None):
         """The whole Autoencoder step in one graph, whichever reconstruction loss the model has: the
         plain MSE on the ELBO kernel (M_N = 0), or the centre-weighted MSE / MS-SSIM on vae_recon_loss
         (loss terms, per-image MSE and the dL/drecon seed of the fused backward)."""
         step = super().fused_train_step(batch, 0.0, lr, weight_decay, betas, graph, process_group, opt,
-                                        plan_options=plan_options)
+                                        plan_options=plan_options, max_grad_norm=max_grad_norm)
         step.plan.eps.zero_()
         step.zero_eps = True
         return step
@@ -962,13 +966,15 @@ class VQVAE(BaseVAE):
 
     def fused_train_step(self, batch: int, kld_weight: float, lr: float, weight_decay: float = 0.0,
                          betas=(0.9, 0.999), graph: bool = True, process_group=None, opt=None,
-                         plan_options: Optional[dict] = None):
+                         plan_options: Optional[dict] = None, max_grad_norm: Optional[float] = None):
         """See _HipVAE.fused_train_step (the VQ-VAE loss ignores kld_weight, vq_vae.py:194-211)."""
         from .engine import FusedAdam, TrainStep
         from .vq import VQStepPlan
         plan = VQStepPlan(self.net, batch, beta=self.beta, **(plan_options or {}))
         if opt is None:
-            opt = FusedAdam(self.net, lr=lr, betas=betas, weight_decay=weight_decay)
+            opt = FusedAdam(self.net, lr=lr, betas=betas, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+        elif max_grad_norm is not None:
+            opt.set_max_grad_norm(max_grad_norm)
         return TrainStep(self.net, plan, opt, graph=graph, process_group=process_group)
 
     def loss_function(self, *args, **kwargs) -> dict:

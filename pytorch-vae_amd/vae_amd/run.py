@@ -12,6 +12,8 @@ the -d / -k overrides follow run.py:39-51.  What differs, on purpose:
     each batch list, flat-gradient all-reduce (mean) after backward, rank-0 BatchNorm buffers;
   * checkpoints are Lightning-format dicts (`state_dict` with `model.`-prefixed reference keys,
     run.py:80-84 `best.ckpt` by val_loss and `last.ckpt`), loadable by the reference and back;
+  * trainer_params.gradient_clip_val (Lightning: clip_grad_norm_ before every optimizer step) is
+    applied only with `--clip_gradients`; without the flag it is ignored with a warning;
   * image outputs of test (draw.py / make_tex.py) are out of scope: test reports loss terms.
 """
 from __future__ import annotations
@@ -48,6 +50,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help='graph: each training step is one replay of the fused HIP-graph step '
                         '(experiment.GraphedSteps); eager: training_step + loss.backward() + optimizer.step()')
     p.add_argument('--max_epochs', type=int, help='override trainer_params.max_epochs')
+    p.add_argument('--clip_gradients', action='store_true', default=False,
+                   help='apply trainer_params.gradient_clip_val (Lightning: clip_grad_norm_ before every '
+                        'optimizer step) on either engine; without it the value is ignored with a warning')
     return p
 
 
@@ -198,15 +203,17 @@ def main(argv=None) -> Dict[str, float]:
             optims, scheds = opt_cfg, []
         best, step = float("inf"), 0
         epochs = config['trainer_params'].get('max_epochs', 1)
-        if config['trainer_params'].get('gradient_clip_val') and rank == 0:
-            # (configs/vae/infovae.yaml sets it; the fused step has no clipping stage — INTEGRATION.md)
+        # configs/vae/infovae.yaml and gammavae.yaml set gradient_clip_val; it is applied only with
+        # --clip_gradients, so a run without the flag trains as it always has
+        clip = (config['trainer_params'].get('gradient_clip_val') or None) if args.clip_gradients else None
+        if config['trainer_params'].get('gradient_clip_val') and not args.clip_gradients and rank == 0:
             warnings.warn("trainer_params.gradient_clip_val is set but not applied by vae_amd.run: "
-                          "gradients are not clipped", stacklevel=1)
+                          "gradients are not clipped (pass --clip_gradients to apply it)", stacklevel=1)
         graphed = None
         if args.engine == 'graph' and hasattr(model, 'fused_train_step') and len(optims) == 1 and _fusable(model):
             # the fused step replayed from HIP graphs (DDP gradient mean and rank-0 buffers inside
-            # the TrainStep); no host synchronisation inside the epoch
-            graphed = GraphedSteps(experiment, optims[0])
+            # the TrainStep, the clip behind them); no host synchronisation inside the epoch
+            graphed = GraphedSteps(experiment, optims[0], clip)
         for epoch in range(epochs):
             model.train()
             sums: Dict[str, float] = {}
@@ -221,6 +228,8 @@ def main(argv=None) -> Dict[str, float]:
                 if world > 1:                                   # DDP: gradient mean, rank-0 buffers
                     allreduce_mean(model.flat.grad)
                     broadcast_buffers(model.net.running)
+                if clip is not None:                            # (after the mean: the same norm on every rank)
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
                 optims[0].step()
                 step += 1
             if graphed is not None:
