@@ -101,13 +101,12 @@ __global__ void __launch_bounds__(256) bn_eval_table_kernel(vae_bn_args a) {
   const int C = x.channels;
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
-  const float mean = x.running_mean[c];
-  const float invstd = 1.0f / sqrtf(x.running_var[c] + x.eps);
-  const float sc = x.gamma[c] * invstd;
-  a.table[c] = sc;
-  a.table[C + c] = x.beta[c] - mean * sc;
-  a.table[2 * C + c] = invstd;
-  a.table[3 * C + c] = -mean * invstd;
+  const BnMom mo = bn_mom_of(x.running_mean[c], x.running_var[c], x.eps);
+  const BnFwd f = bn_fwd(mo, x.gamma[c]);
+  a.table[c] = f.a;
+  a.table[C + c] = f.b(x.beta[c]);
+  a.table[2 * C + c] = f.p;
+  a.table[3 * C + c] = f.q;
 }
 
 }  // namespace

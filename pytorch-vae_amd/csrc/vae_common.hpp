@@ -267,7 +267,54 @@ __device__ __forceinline__ float rsum(const float* a, const vae_xform& x, int c)
   return acc;
 }
 
-// mean/invstd/var of channel c from the producer's Σ(y-shift), Σ(y-shift)^2.
+// The BatchNorm coefficient arithmetic, once: pure functions of scalars.  Every table builder
+//  loads and reduces its replicas its own way and calls these for the rest.
+struct BnMom { float mean, invstd, var; };
+struct BnFwd {                            // v = lrelu(y*a + b), x̂ = y*p + q
+  float a, p, q, mean;
+  // b takes beta, so a builder that stores a before it loads beta can go on doing so
+  __device__ __forceinline__ float b(float beta) const { return beta - mean * a; }
+};
+struct BnBwd { float A, B, C; };          // dy = A*g + B*y + C
+
+__device__ __forceinline__ BnMom bn_mom_of(float mean, float var, float eps) {
+  return {mean, 1.0f / sqrtf(var + eps), var};
+}
+// from the producer's channel totals Σ(y-shift), Σ(y-shift)^2
+__device__ __forceinline__ BnMom bn_mom(float sum, float sumsq, float shift, const vae_xform& x) {
+  const float inv_m = 1.0f / x.count;
+  const float s1 = sum * inv_m;
+  const float var = fmaxf(sumsq * inv_m - s1 * s1, 0.0f);
+  return bn_mom_of(s1 + shift, var, x.eps);
+}
+__device__ __forceinline__ BnFwd bn_fwd(const BnMom& m, float gamma) {
+  return {gamma * m.invstd, m.invstd, -m.mean * m.invstd, m.mean};
+}
+// The running statistics move by bn_momentum, the mean towards the batch mean and the variance
+// towards the unbiased batch variance (a builder takes that first, then load, store, load, store).
+__device__ __forceinline__ float bn_unbiased(const BnMom& m, const vae_xform& x) {
+  return x.count > 1.f ? m.var * x.count / (x.count - 1.f) : m.var;
+}
+__device__ __forceinline__ float bn_momentum(const vae_xform& x, float old, float batch) {
+  const float m = x.momentum;
+  return (1.f - m) * old + m * batch;
+}
+// from the channel totals Σ g*x̂ (vae_xform.dgamma) and Σ g (vae_xform.dbeta)
+__device__ __forceinline__ BnBwd bn_bwd(const BnMom& m, float gamma, float sum_gx, float sum_g, const vae_xform& x) {
+  const float inv_m = 1.0f / x.count;
+  const float A = gamma * m.invstd;
+  const float mg = sum_g * inv_m, mgx = sum_gx * inv_m;
+  return {A, -A * m.invstd * mgx, -A * (mg - m.mean * m.invstd * mgx)};
+}
+// closed-form bias gradient of a conv followed by train-mode BatchNorm: Σ dy = A·Σg + B·Σy + C·M
+__device__ __forceinline__ float bn_db(const BnBwd& k, float sum_g, float sum, float shift, float count) {
+  const float sum_y = sum + count * shift;
+  return k.A * sum_g + k.B * sum_y + k.C * count;
+}
+
+// mean/invstd/var of channel c from the producer's Σ(y-shift), Σ(y-shift)^2: rsum x2 and bn_mom's
+// arithmetic, restated here so that each sum is scaled as it arrives (through bn_mom the GEMM
+// kernels allocate other registers: DESIGN.md §5).
 __device__ __forceinline__ void bn_moments(const vae_xform& x, int c, float& mean, float& invstd, float& var) {
   const float inv_m = 1.0f / x.count;
   const float s = rsum(x.sum, x, c) * inv_m;
@@ -275,46 +322,6 @@ __device__ __forceinline__ void bn_moments(const vae_xform& x, int c, float& mea
   mean = s + (x.shift ? x.shift[c] : 0.0f);
   invstd = 1.0f / sqrtf(var + x.eps);
 }
-
-// Per-channel coefficient table in LDS for one transform.
-//   BN_ACT: v = lrelu(t*a + b)         ACT: v = lrelu(t)        NONE: v = t
-//   BN_DY : v = a*t + b*aux + c
-//   epilogue use (BN_ACT): also p,q with xhat = y*p + q
-template <int MAXC, bool EPI>
-struct XfTable {
-  float a[MAXC], b[MAXC], c[MAXC];
-  float p[EPI ? MAXC : 1], q[EPI ? MAXC : 1];
-
-  // Fill for channels [0, C); optionally update BN running stats (one block only).
-  __device__ __forceinline__ void fill(const vae_xform& x, bool update_running) {
-    if (x.kind != VAE_X_BN_ACT && x.kind != VAE_X_BN_DY) return;
-    for (int ch = threadIdx.x; ch < x.channels; ch += blockDim.x) {
-      float mean, invstd, var;
-      bn_moments(x, ch, mean, invstd, var);
-      const float g = x.gamma[ch];
-      if (x.kind == VAE_X_BN_ACT) {
-        const float sc = g * invstd;
-        a[ch] = sc;
-        b[ch] = x.beta[ch] - mean * sc;
-        if (EPI) { p[EPI ? ch : 0] = invstd; q[EPI ? ch : 0] = -mean * invstd; }
-        if (update_running && x.running_mean) {
-          const float m = x.momentum;
-          const float unb = x.count > 1.f ? var * x.count / (x.count - 1.f) : var;
-          x.running_mean[ch] = (1.f - m) * x.running_mean[ch] + m * mean;
-          x.running_var[ch] = (1.f - m) * x.running_var[ch] + m * unb;
-        }
-      } else {
-        const float inv_m = 1.0f / x.count;
-        const float A = g * invstd;
-        const float mg = rsum(x.dbeta, x, ch) * inv_m;         // mean of g
-        const float mgx = rsum(x.dgamma, x, ch) * inv_m;       // mean of g*xhat
-        a[ch] = A;
-        b[ch] = -A * invstd * mgx;
-        c[ch] = -A * (mg - mean * invstd * mgx);
-      }
-    }
-  }
-};
 
 // ---------------------------------------------------------------- BatchNorm finalisation
 // The per-step BatchNorm table (vae_bn_args, vaehip.h) for channel groups cg0, cg0+cgs, ... of
@@ -359,38 +366,27 @@ __device__ __forceinline__ void bn_finalize_block(const vae_bn_args& a, int cg0,
       float tot[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) tot[k] = (red[k][0][cl] + red[k][1][cl]) + (red[k][2][cl] + red[k][3][cl]);
-      const float inv_m = 1.0f / x.count;
-      const float s1 = tot[0] * inv_m;
-      const float var = fmaxf(tot[1] * inv_m - s1 * s1, 0.0f);
-      const float mean = s1 + sh;
-      const float invstd = 1.0f / sqrtf(var + x.eps);
+      const BnMom mo = bn_mom(tot[0], tot[1], sh, x);
       if (!bwd) {
-        const float sc = g * invstd;
-        a.table[c] = sc;
-        a.table[C + c] = be - mean * sc;
-        a.table[2 * C + c] = invstd;
-        a.table[3 * C + c] = -mean * invstd;
+        const BnFwd f = bn_fwd(mo, g);
+        a.table[c] = f.a;
+        a.table[C + c] = f.b(be);
+        a.table[2 * C + c] = f.p;
+        a.table[3 * C + c] = f.q;
         if (run) {
-          const float m = x.momentum;
-          const float unb = x.count > 1.f ? var * x.count / (x.count - 1.f) : var;
-          x.running_mean[c] = (1.f - m) * rmean + m * mean;
-          x.running_var[c] = (1.f - m) * rvar + m * unb;
+          const float unb = bn_unbiased(mo, x);
+          x.running_mean[c] = bn_momentum(x, rmean, mo.mean);
+          x.running_var[c] = bn_momentum(x, rvar, unb);
         }
       } else {
         const float dgam = tot[2], dbet = tot[3];
-        const float A = g * invstd;
-        const float mgx = dgam * inv_m, mg = dbet * inv_m;
-        const float B = -A * invstd * mgx;
-        const float Cc = -A * (mg - mean * invstd * mgx);
-        a.table[c] = A;
-        a.table[C + c] = B;
-        a.table[2 * C + c] = Cc;
+        const BnBwd k = bn_bwd(mo, g, dgam, dbet, x);
+        a.table[c] = k.A;
+        a.table[C + c] = k.B;
+        a.table[2 * C + c] = k.C;
         if (x.dgamma_out) x.dgamma_out[c] += dgam;
         if (x.dbeta_out) x.dbeta_out[c] += dbet;
-        if (a.db) {
-          const float sum_y = tot[0] + x.count * sh;
-          a.db[c] += A * dbet + B * sum_y + Cc * x.count;
-        }
+        if (a.db) a.db[c] += bn_db(k, dbet, tot[0], sh, x.count);
       }
     }
     __syncthreads();
@@ -502,28 +498,27 @@ __device__ __forceinline__ void tab_pre_finish(const vae_xform& x, const TabPre<
     const float g = j == 0 ? q.g : x.gamma[ch];
     const float be = j == 0 ? q.be : x.beta[ch];
     const float sh = j == 0 ? q.sh : (x.shift ? x.shift[ch] : 0.0f);
-    const float inv_m = 1.0f / x.count;
-    const float s1 = tot[j][0] * inv_m;
-    const float var = fmaxf(tot[j][1] * inv_m - s1 * s1, 0.0f);
-    const float mean = s1 + sh;
-    const float invstd = 1.0f / sqrtf(var + x.eps);
+    const BnMom mo = bn_mom(tot[j][0], tot[j][1], sh, x);
     if (x.kind == VAE_X_BN_ACT) {
-      const float sc = g * invstd;
-      t.a[ch] = sc;
-      t.b[ch] = be - mean * sc;
-      if (epi) { t.p[ch] = invstd; t.q[ch] = -mean * invstd; }
+      const BnFwd f = bn_fwd(mo, g);
+      t.a[ch] = f.a;
+      t.b[ch] = f.b(be);
+      if (epi) { t.p[ch] = f.p; t.q[ch] = f.q; }
       if (update_running && x.running_mean) {
+        // bn_unbiased and bn_momentum, restated: momentum is read first
         const float m = x.momentum;
-        const float unb = x.count > 1.f ? var * x.count / (x.count - 1.f) : var;
-        x.running_mean[ch] = (1.f - m) * x.running_mean[ch] + m * mean;
+        const float unb = x.count > 1.f ? mo.var * x.count / (x.count - 1.f) : mo.var;
+        x.running_mean[ch] = (1.f - m) * x.running_mean[ch] + m * mo.mean;
         x.running_var[ch] = (1.f - m) * x.running_var[ch] + m * unb;
       }
     } else {
-      const float A = g * invstd;
+      // bn_bwd, restated: A is stored before B and C are formed
+      const float inv_m = 1.0f / x.count;
+      const float A = g * mo.invstd;
       const float mg = tot[j][3] * inv_m, mgx = tot[j][2] * inv_m;
       t.a[ch] = A;
-      t.b[ch] = -A * invstd * mgx;
-      t.c[ch] = -A * (mg - mean * invstd * mgx);
+      t.b[ch] = -A * mo.invstd * mgx;
+      t.c[ch] = -A * (mg - mo.mean * mo.invstd * mgx);
     }
   }
 }

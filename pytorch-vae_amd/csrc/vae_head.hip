@@ -118,15 +118,15 @@ __device__ void head_tables(const vae_xform& xf, float* ta, float* tb, float* tp
     if (xf.table) {
       ta[c] = xf.table[cg]; tb[c] = xf.table[CT + cg]; tp[c] = xf.table[2 * CT + cg]; tq[c] = xf.table[3 * CT + cg];
     } else {
-      float mean, invstd, var;
-      bn_moments(xf, cg, mean, invstd, var);
-      ta[c] = xf.gamma[cg] * invstd; tb[c] = xf.beta[cg] - mean * ta[c];
-      tp[c] = invstd; tq[c] = -mean * invstd;
+      BnMom mo;
+      bn_moments(xf, cg, mo.mean, mo.invstd, mo.var);
+      const BnFwd f = bn_fwd(mo, xf.gamma[cg]);
+      ta[c] = f.a; tb[c] = f.b(xf.beta[cg]);
+      tp[c] = f.p; tq[c] = f.q;
       if (update_running && xf.running_mean) {     // (C = 128: 32 statistic replicas, no tab_build)
-        const float m = xf.momentum;
-        const float unb = xf.count > 1.f ? var * xf.count / (xf.count - 1.f) : var;
-        xf.running_mean[cg] = (1.f - m) * xf.running_mean[cg] + m * mean;
-        xf.running_var[cg] = (1.f - m) * xf.running_var[cg] + m * unb;
+        const float unb = bn_unbiased(mo, xf);
+        xf.running_mean[cg] = bn_momentum(xf, xf.running_mean[cg], mo.mean);
+        xf.running_var[cg] = bn_momentum(xf, xf.running_var[cg], unb);
       }
     }
   }

@@ -48,16 +48,16 @@ __device__ void head_coefs(const vae_xform& xf, float* ta, float* tb, float* tp,
     return;
   }
   for (int ch = threadIdx.x; ch < xf.channels; ch += blockDim.x) {
-    float mean, invstd, var;
-    bn_moments(xf, ch, mean, invstd, var);
-    ta[ch] = xf.gamma[ch] * invstd;
-    tb[ch] = xf.beta[ch] - mean * ta[ch];
-    if (tp) { tp[ch] = invstd; tq[ch] = -mean * invstd; }
+    BnMom mo;
+    bn_moments(xf, ch, mo.mean, mo.invstd, mo.var);
+    const BnFwd f = bn_fwd(mo, xf.gamma[ch]);
+    ta[ch] = f.a;
+    tb[ch] = f.b(xf.beta[ch]);
+    if (tp) { tp[ch] = f.p; tq[ch] = f.q; }
     if (update_running && xf.running_mean) {
-      const float m = xf.momentum;
-      const float unb = xf.count > 1.f ? var * xf.count / (xf.count - 1.f) : var;
-      xf.running_mean[ch] = (1.f - m) * xf.running_mean[ch] + m * mean;
-      xf.running_var[ch] = (1.f - m) * xf.running_var[ch] + m * unb;
+      const float unb = bn_unbiased(mo, xf);
+      xf.running_mean[ch] = bn_momentum(xf, xf.running_mean[ch], mo.mean);
+      xf.running_var[ch] = bn_momentum(xf, xf.running_var[ch], unb);
     }
   }
 }

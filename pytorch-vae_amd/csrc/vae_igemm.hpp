@@ -151,16 +151,21 @@ __device__ __forceinline__ PhaseInfo make_phase(const GemmParams& p, int phase) 
 }
 
 // ------------------------------------------------------------------ per-channel tables
-// Fill a transform table (vae_common.hpp Tab): a copy of vae_bn_finalize's precomputed table, or
-// built by this workgroup from the producer's replicated statistics (tab_build).
-// scr: 1024 floats of LDS scratch for the replica reduction, free for the duration of the call.
-__device__ __forceinline__ void tab_fill(const vae_xform& x, Tab t, bool epi, bool update_running, float* scr) {
-  if (x.kind != VAE_X_BN_ACT && x.kind != VAE_X_BN_DY) return;
+// The eight zero-slot entries behind each row of a table (tab_stride).
+__device__ __forceinline__ void tab_zero_slot(const vae_xform& x, Tab t) {
   if (threadIdx.x < 8) {
     const int z = tab_pad(x.channels) + threadIdx.x;
     t.a[z] = 0.f; t.b[z] = 0.f;
     if (x.kind == VAE_X_BN_DY) t.c[z] = 0.f;
   }
+}
+
+// Fill a transform table (vae_common.hpp Tab): a copy of vae_bn_finalize's precomputed table, or
+// built by this workgroup from the producer's replicated statistics (tab_build).
+// scr: 1024 floats of LDS scratch for the replica reduction, free for the duration of the call.
+__device__ __forceinline__ void tab_fill(const vae_xform& x, Tab t, bool epi, bool update_running, float* scr) {
+  if (x.kind != VAE_X_BN_ACT && x.kind != VAE_X_BN_DY) return;
+  tab_zero_slot(x, t);
   if (x.table) {
     // precomputed by vae_bn_finalize: one coalesced copy, four channels of a thread per round of
     // loads (the Autoencoder's 4096-channel tables: 4 rounds, not 16 dependent ones)
@@ -193,28 +198,28 @@ __device__ __forceinline__ void tab_fill(const vae_xform& x, Tab t, bool epi, bo
     return;
   }
   for (int ch = threadIdx.x; ch < x.channels; ch += blockDim.x) {
-    float mean, invstd, var;
-    bn_moments(x, ch, mean, invstd, var);
+    BnMom mo;
+    bn_moments(x, ch, mo.mean, mo.invstd, mo.var);
     const float g = x.gamma[ch];
     if (x.kind == VAE_X_BN_ACT) {
-      const float sc = g * invstd;
-      t.a[ch] = sc;
-      t.b[ch] = x.beta[ch] - mean * sc;
-      if (epi) { t.p[ch] = invstd; t.q[ch] = -mean * invstd; }
+      const BnFwd f = bn_fwd(mo, g);
+      t.a[ch] = f.a;
+      t.b[ch] = f.b(x.beta[ch]);
+      if (epi) { t.p[ch] = f.p; t.q[ch] = f.q; }
       if (update_running && x.running_mean) {
-        const float m = x.momentum;
-        const float unb = x.count > 1.f ? var * x.count / (x.count - 1.f) : var;
-        x.running_mean[ch] = (1.f - m) * x.running_mean[ch] + m * mean;
-        x.running_var[ch] = (1.f - m) * x.running_var[ch] + m * unb;
+        const float unb = bn_unbiased(mo, x);
+        x.running_mean[ch] = bn_momentum(x, x.running_mean[ch], mo.mean);
+        x.running_var[ch] = bn_momentum(x, x.running_var[ch], unb);
       }
     } else {
+      // bn_bwd, restated: A is stored before B and C are formed
       const float inv_m = 1.0f / x.count;
-      const float A = g * invstd;
+      const float A = g * mo.invstd;
       const float mg = rsum(x.dbeta, x, ch) * inv_m;         // mean of g
       const float mgx = rsum(x.dgamma, x, ch) * inv_m;       // mean of g*xhat
       t.a[ch] = A;
-      t.b[ch] = -A * invstd * mgx;
-      t.c[ch] = -A * (mg - mean * invstd * mgx);
+      t.b[ch] = -A * mo.invstd * mgx;
+      t.c[ch] = -A * (mg - mo.mean * mo.invstd * mgx);
     }
   }
 }
@@ -235,11 +240,7 @@ template <int NS>
 __device__ __forceinline__ void tab_fill_pre(const vae_xform& x, const TabPre<NS>& q, bool pre, Tab t, bool epi,
                                              bool update_running, float* scr) {
   if (!pre) { tab_fill(x, t, epi, update_running, scr); return; }
-  if (threadIdx.x < 8) {
-    const int z = tab_pad(x.channels) + threadIdx.x;
-    t.a[z] = 0.f; t.b[z] = 0.f;
-    if (x.kind == VAE_X_BN_DY) t.c[z] = 0.f;
-  }
+  tab_zero_slot(x, t);
   tab_pre_finish(x, q, t, epi, update_running, scr);
 }
 
@@ -818,20 +819,15 @@ __device__ __forceinline__ void epi_flush_sums(const GemmParams& p, int rep, int
 // also publishes the reduced BatchNorm affine gradients (dgamma_out / dbeta_out) when asked.
 __device__ __forceinline__ void closed_form_db(const vae_xform& x, float* db) {
   for (int ch = threadIdx.x; ch < x.channels; ch += blockDim.x) {
-    float mean, invstd, var;
-    bn_moments(x, ch, mean, invstd, var);
-    const float inv_m = 1.0f / x.count;
+    BnMom mo;
+    bn_moments(x, ch, mo.mean, mo.invstd, mo.var);
     const float dgam = rsum(x.dgamma, x, ch), dbet = rsum(x.dbeta, x, ch);
     if (x.dgamma_out) x.dgamma_out[ch] += dgam;
     if (x.dbeta_out) x.dbeta_out[ch] += dbet;
     if (!db) continue;
-    const float A = x.gamma[ch] * invstd;
-    const float mgx = dgam * inv_m;
-    const float mg = dbet * inv_m;
-    const float B = -A * invstd * mgx;
-    const float C = -A * (mg - mean * invstd * mgx);
-    const float sum_y = rsum(x.sum, x, ch) + x.count * (x.shift ? x.shift[ch] : 0.f);
-    db[ch] += A * dbet + B * sum_y + C * x.count;
+    const BnBwd k = bn_bwd(mo, x.gamma[ch], dgam, dbet, x);
+    const float sum = rsum(x.sum, x, ch);
+    db[ch] += bn_db(k, dbet, sum, x.shift ? x.shift[ch] : 0.f, x.count);
   }
 }
 

@@ -98,20 +98,13 @@ __device__ __forceinline__ BnCoef bn_coef(const vae_xform& x, int c, bool update
       tq += r0 + u < R ? q[u] : 0.f;
     }
   }
-  const float inv_m = 1.0f / x.count;
-  const float s1 = ts * inv_m;
-  const float var = fmaxf(tq * inv_m - s1 * s1, 0.0f);
-  const float mean = s1 + sh;
-  const float invstd = 1.0f / sqrtf(var + x.eps);
-  k.a = g * invstd;
-  k.b = be - mean * k.a;
-  k.p = invstd;
-  k.q = -mean * invstd;
+  const BnMom mo = bn_mom(ts, tq, sh, x);
+  const BnFwd f = bn_fwd(mo, g);
+  k.a = f.a; k.b = f.b(be); k.p = f.p; k.q = f.q;
   if (update_running && x.running_mean) {
-    const float m = x.momentum;
-    const float unb = x.count > 1.f ? var * x.count / (x.count - 1.f) : var;
-    x.running_mean[c] = (1.f - m) * x.running_mean[c] + m * mean;
-    x.running_var[c] = (1.f - m) * x.running_var[c] + m * unb;
+    const float unb = bn_unbiased(mo, x);
+    x.running_mean[c] = bn_momentum(x, x.running_mean[c], mo.mean);
+    x.running_var[c] = bn_momentum(x, x.running_var[c], unb);
   }
   return k;
 }
