@@ -794,6 +794,57 @@ typedef struct vae_recon_loss_args {
 int vae_recon_loss(const vae_recon_loss_args* a, void* stream);
 int vae_recon_loss_workspace_size(const vae_recon_loss_args* a, size_t* bytes);
 
+/* --- LogCoshVAE's loss: log-cosh reconstruction term + KL, forward + backward seeds ---------------
+ * models/logcosh_vae.py:125-155.  With t = recon - target over n images of `elems` = c*h*w fp32 values
+ * (NCHW, contiguous) and N = n*elems:
+ *   Reconstruction_Loss = (1/alpha) * mean(alpha*t + log(1 + exp(-2*alpha*t)) - log 2)
+ *   evaluated per element in the stable form  a = |t|, e = exp(-2*alpha*a),
+ *     f = a + (log1p(e) - ln 2) / alpha,   tanh(alpha*t) = copysign((1 - e) / (1 + e), t)
+ *   (one exp for both; accurate expf / log1pf).  f equals the reference's expression wherever that is
+ *   finite in fp32; the reference overflows to inf once -2*alpha*t > 88.7 (alpha = 100, its
+ *   constructor default: every t < -0.44), this form is finite for every finite t.
+ *   grad (if set) [n][elems] = grad_scale * tanh(alpha*t) / N: dL/drecon, the seed of the fused
+ *   backward (vae_head_args.grad_recon / vae_recon_args.grad_recon).
+ * With mulv ([n][2*latent] = mu | log_var) the KL term and its seed are evaluated in the same call:
+ *   kld_b = -0.5 Σ_d (1 + lv - mu^2 - e^lv), kld = mean_b kld_b (the per-row arithmetic of
+ *   vae_elbo_fwd), loss = Reconstruction_Loss + kl_weight*kld; the caller passes kl_weight = beta*M_N;
+ *   out[4] = {loss, Reconstruction_Loss, -kld (as the reference reports it), kld};
+ *   kl_coef[b] = kl_weight / n, b < n: the per-row coefficient vae_latent_dec_bwd /
+ *   vae_linear_bwd_data multiply into mu and 0.5*(e^lv - 1) (kl_coef is not scaled by grad_scale).
+ * With mulv NULL: out = {Reconstruction_Loss, Reconstruction_Loss, 0, 0}; kl_coef is not touched.
+ * per_img (if set with sse) [n] = sse / elems, the per-image MSE of experiment.py:60-62.
+ * Two launches, no atomics (repeated calls are bit-identical): workgroups stream recon and target
+ * (16-byte accesses when recon, target and grad are 16-byte aligned, the last n*elems % 4 elements —
+ * or, unaligned, all of them — one at a time), write grad and leave one partial sum each as a double
+ * in the workspace; one workgroup then adds the partials (each thread every 256th one in ascending
+ * order, the 256 sums in a fixed tree), evaluates the KL rows in a fixed order and writes out,
+ * kl_coef and per_img.
+ * VAE_E_BADSHAPE: n < 1, elems < 1, mulv set with latent < 1.  VAE_E_BADARG: alpha not finite or
+ * <= 0, null recon / target / out, mulv set without kl_coef, a workspace that is NULL, not 8-byte
+ * aligned or smaller than vae_logcosh_loss_workspace_size.  Each has its own reason, checked before
+ * any launch. */
+typedef struct vae_logcosh_args {
+  int32_t n;                 /* images */
+  int32_t latent;            /* with mulv */
+  int64_t elems;             /* c*h*w values per image */
+  float alpha;
+  float grad_scale;
+  float kl_weight;           /* beta * M_N */
+  int32_t reserved;
+  const float* recon;        /* [n][elems] */
+  const float* target;       /* [n][elems] */
+  float* grad;               /* optional [n][elems] */
+  const float* mulv;         /* optional [n][2*latent] */
+  float* out;                /* [4] */
+  float* kl_coef;            /* [n], with mulv */
+  const float* sse;          /* optional [n] */
+  float* per_img;            /* optional [n] */
+  void* workspace;
+  int64_t workspace_bytes;
+} vae_logcosh_args;
+int vae_logcosh_loss(const vae_logcosh_args* a, void* stream);
+int vae_logcosh_loss_workspace_size(const vae_logcosh_args* a, size_t* bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,29 +59,38 @@ __device__ __forceinline__ float elbo_group(const vae_elbo_args& a, const float*
   }
 }
 
+// kld_b = -0.5 Σ_d (1 + lv - mu^2 - exp(lv)) of row b = b0 + (threadIdx.x >> 2), one pass of a
+// 256-thread workgroup over 64 rows of mulv [B][2*D]: 4 threads per row, each a quarter of the latent
+// dims with all its loads in flight at once.  Every one of a row's 4 threads returns kld_b (0 past
+// the batch).  The one home of this arithmetic: elbo_block below and vae_logcosh_loss call it.
+__device__ __forceinline__ float kld_row_pass(const float* mulv, int B, int D, int b0) {
+  const int part = threadIdx.x & 3, per = (D + 3) / 4;
+  const int b = b0 + (threadIdx.x >> 2);
+  float s = 0.f;
+  if (b < B) {
+    const float* mu = mulv + (long)b * 2 * D;
+    const float* lv = mu + D;
+    const int d0 = part * per, d1 = min(D, d0 + per);
+#pragma unroll 32
+    for (int d = d0; d < d1; ++d) s += 1.f + lv[d] - mu[d] * mu[d] - expf(lv[d]);
+  }
+  s += __shfl_xor(s, 1);
+  s += __shfl_xor(s, 2);
+  return -0.5f * s;
+}
+
 // The loss of vaehip.h vae_elbo_fwd by one 256-thread workgroup (kld_row: 1024 floats of LDS, red:
 // 16) — run by elbo_kernel, and by the head backward's slab-reduction launch when the step fuses it
 // (vae_head_args.elbo).
 __device__ __forceinline__ void elbo_block(const vae_elbo_args& a, float* kld_row, float (*red)[4]) {
   const int B = a.batch, S = a.samples > 0 ? a.samples : 1, D = a.latent;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  // kld_b = -0.5 Σ_d (1 + lv - mu^2 - exp(lv)): 4 threads per row, each a quarter of the latent
-  // dims with all its loads in flight at once (64 rows per pass)
+  // kld_b of every row (kld_row_pass: 64 rows per pass)
   if (a.kind != VAE_LOSS_VQ) {
-    const int part = threadIdx.x & 3, per = (D + 3) / 4;
     for (int b0 = 0; b0 < B; b0 += 64) {
       const int b = b0 + (threadIdx.x >> 2);
-      float s = 0.f;
-      if (b < B) {
-        const float* mu = a.mulv + (long)b * 2 * D;
-        const float* lv = mu + D;
-        const int d0 = part * per, d1 = min(D, d0 + per);
-#pragma unroll 32
-        for (int d = d0; d < d1; ++d) s += 1.f + lv[d] - mu[d] * mu[d] - expf(lv[d]);
-      }
-      s += __shfl_xor(s, 1);
-      s += __shfl_xor(s, 2);
-      if (part == 0 && b < B) kld_row[b] = -0.5f * s;
+      const float k = kld_row_pass(a.mulv, B, D, b0);
+      if ((threadIdx.x & 3) == 0 && b < B) kld_row[b] = k;
     }
   }
   __syncthreads();

@@ -158,6 +158,15 @@ class ReconLossArgs(ctypes.Structure):
 RLOSS_CENTER, RLOSS_MSSIM = 0, 1
 
 
+class LogCoshArgs(ctypes.Structure):
+    """vaehip.h vae_logcosh_args (LogCoshVAE's log-cosh reconstruction term + KL, with their seeds)."""
+    _fields_ = [("n", c_int32), ("latent", c_int32), ("elems", c_int64), ("alpha", c_float),
+                ("grad_scale", c_float), ("kl_weight", c_float), ("reserved", c_int32),
+                ("recon", c_void_p), ("target", c_void_p), ("grad", c_void_p), ("mulv", c_void_p),
+                ("out", c_void_p), ("kl_coef", c_void_p), ("sse", c_void_p), ("per_img", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", c_int64)]
+
+
 class RecordArgs(ctypes.Structure):
     _fields_ = [("batch", c_int32), ("samples", c_int32), ("img_elems", c_int32), ("nterms", c_int32),
                 ("step", c_int32), ("src_terms", c_void_p), ("terms", c_void_p), ("per_img", c_void_p),
@@ -264,6 +273,8 @@ _SIGS = {
     "vae_recon_loss": [POINTER(ReconLossArgs), c_void_p],
     "vae_bn_apply": [POINTER(BnApplyArgs), c_void_p],
     "vae_recon_loss_workspace_size": [POINTER(ReconLossArgs), POINTER(ctypes.c_size_t)],
+    "vae_logcosh_loss": [POINTER(LogCoshArgs), c_void_p],
+    "vae_logcosh_loss_workspace_size": [POINTER(LogCoshArgs), POINTER(ctypes.c_size_t)],
 }
 EXPORTED = tuple(_SIGS)
 
@@ -415,6 +426,14 @@ def recon_loss_args(kind: int, n: int, c: int, h: int, w: int, *, mask=None, win
     return a
 
 
+def logcosh_args(n: int, elems: int, alpha: float, *, kl_weight: float = 0.0, latent: int = 0,
+                 grad_scale: float = 1.0) -> "LogCoshArgs":
+    """A vae_logcosh_loss argument block with the loss's constants filled in (pointers left to the
+    caller): `n` images of `elems` values, LogCoshVAE's alpha, and for a call with mulv the latent
+    size and kl_weight = beta * M_N."""
+    return LogCoshArgs(n=n, elems=elems, alpha=alpha, grad_scale=grad_scale, kl_weight=kl_weight, latent=latent)
+
+
 def mmd_workspace(a: "MmdArgs"):
     """(bytes of partials, tile count) of a vae_mmd_fwd call (vae_mmd_workspace_size; no device)."""
     out, tiles = ctypes.c_size_t(0), c_int32(0)
@@ -432,4 +451,11 @@ def dip_workspace(a: "DipArgs"):
 def recon_loss_workspace(a: "ReconLossArgs") -> int:
     out = ctypes.c_size_t(0)
     call("vae_recon_loss_workspace_size", ctypes.byref(a), ctypes.byref(out))
+    return int(out.value)
+
+
+def logcosh_workspace(a: "LogCoshArgs") -> int:
+    """Workspace bytes of a vae_logcosh_loss call (vae_logcosh_loss_workspace_size; no device)."""
+    out = ctypes.c_size_t(0)
+    call("vae_logcosh_loss_workspace_size", ctypes.byref(a), ctypes.byref(out))
     return int(out.value)

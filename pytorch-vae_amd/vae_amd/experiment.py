@@ -361,8 +361,8 @@ class GraphedSteps:
 
 def _fusable(model) -> bool:
     """Models whose whole step the fused engine computes: every model with fused_train_step — the
-    Autoencoder's centre-weighted MSE and MS-SSIM included (vae_recon_loss inside the step), except
-    an MS-SSIM configured outside the kernel's range (size_average=False, windows > 15)."""
+    Autoencoder's centre-weighted MSE and MS-SSIM (vae_recon_loss inside the step) and LogCoshVAE's
+    log-cosh term (vae_logcosh_loss) included, except an MS-SSIM configured outside the kernel's range (size_average=False, windows > 15)."""
     m = getattr(model, "mssim", None)
     return m is None or (m.size_average and m.window_size <= 15)
 

@@ -9,6 +9,7 @@ Mirrors the reference interface (paths relative to the reference root):
   InfoVAE                 models/info_vae.py:8-256  (MMD term on vae_mmd_fwd; imq / rbf kernels)
   DIPVAE                  models/dip_vae.py:8-191   (covariance penalty of the means on vae_dip_fwd)
   MIWAE                   models/miwae.py:8-192     (num_estimates x num_samples; rows in b, m, k order)
+  LogCoshVAE              models/logcosh_vae.py:8-176 (log-cosh reconstruction term on vae_logcosh_loss)
   VQVAE                   models/vq_vae.py:73-219   (VectorQuantizer, residual stacks; vae_amd/vq.py)
   vae_models registry     models/__init__.py:35-56
 
@@ -218,6 +219,30 @@ class _HipReconLoss(torch.autograd.Function):
         L.call("vae_recon_loss", a, L.stream_ptr())
         ctx.save_for_backward(grad)
         return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class _HipLogCosh(torch.autograd.Function):
+    """LogCoshVAE's reconstruction term (1/alpha) mean log cosh(alpha (recons - input)) on the GPU
+    (vaehip.h vae_logcosh_loss, called without mulv): forward evaluates the term and dL/drecons =
+    tanh(alpha t) / N in one call; backward scales that seed by dL/dloss."""
+
+    @staticmethod
+    def forward(ctx, recons: Tensor, target: Tensor, alpha: float):
+        recons, target = recons.detach().float().contiguous(), target.detach().float().contiguous()
+        a = L.logcosh_args(recons.shape[0], recons[0].numel(), alpha)
+        grad = torch.empty_like(recons)
+        out = torch.zeros(4, dtype=torch.float32, device=recons.device)
+        ws = torch.empty(max(1, L.logcosh_workspace(a) // 8), dtype=torch.float64, device=recons.device)
+        a.recon, a.target, a.grad, a.out = recons.data_ptr(), target.data_ptr(), grad.data_ptr(), out.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        L.call("vae_logcosh_loss", a, L.stream_ptr())
+        ctx.save_for_backward(grad)
+        return out[1].clone()
 
     @staticmethod
     def backward(ctx, g):
@@ -595,6 +620,44 @@ class DIPVAE(_HipVAE):
                     + self.lambda_diag * torch.sum((cov_diag - 1) ** 2))
         loss = recons_loss + kld_weight * kld_loss + dip_loss
         return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'KLD': -kld_loss, 'DIP_Loss': dip_loss}
+
+
+class LogCoshVAE(_HipVAE):
+    """models/logcosh_vae.py:8-176 on libvaehip: the VanillaVAE network with the loss
+    (1/alpha) mean log cosh(alpha (recons - input)) + beta * M_N * kld.  The reconstruction term is
+    evaluated in the stable form a + (log1p(exp(-2 alpha a)) - log 2) / alpha, a = |t|: it equals the
+    reference's expression wherever that is finite in fp32 and stays finite where the reference's
+    exp(-2 alpha t) overflows (alpha = 100, the constructor default: every t < -0.44)."""
+
+    def __init__(self, in_channels: int, latent_dim: int, hidden_dims: List = None, alpha: float = 100.,
+                 beta: float = 10., **kwargs) -> None:
+        super().__init__(in_channels, latent_dim, hidden_dims, **kwargs)
+        self.alpha = alpha
+        self.beta = beta
+
+    def _loss_config(self) -> dict:
+        return dict(loss="logcosh", alpha=float(self.alpha), beta=float(self.beta))
+
+    def _dropin_config(self) -> dict:
+        return _HipVAE._loss_config(self)       # (the log-cosh term and the KL run in loss_function)
+
+    @staticmethod
+    def logcosh(t: Tensor, alpha: float) -> Tensor:
+        """(1/alpha) log cosh(alpha t) per element, stable form (logcosh_vae.py:146-148 where that is finite)."""
+        a = t.abs()
+        return a + (torch.log1p(torch.exp(-2.0 * alpha * a)) - math.log(2.0)) / alpha
+
+    def loss_function(self, *args, **kwargs) -> dict:
+        """logcosh_vae.py:125-155."""
+        recons, input, mu, log_var = args[0], args[1], args[2], args[3]
+        kld_weight = kwargs['M_N']
+        if recons.is_cuda and recons.dim() == 4 and recons.shape == input.shape and float(self.alpha) > 0.0:
+            recons_loss = _HipLogCosh.apply(recons, input, float(self.alpha))   # vae_logcosh_loss (forward + seed)
+        else:
+            recons_loss = self.logcosh(recons - input, self.alpha).mean()
+        kld_loss = torch.mean(-0.5 * torch.sum(1 + log_var - mu ** 2 - log_var.exp(), dim=1), dim=0)
+        loss = recons_loss + self.beta * kld_weight * kld_loss
+        return {'loss': loss, 'Reconstruction_Loss': recons_loss, 'KLD': -kld_loss}
 
 
 class MIWAE(_HipVAE):
@@ -993,7 +1056,7 @@ class VQVAE(BaseVAE):
 
 # models/__init__.py:35-56: the families on the MI355X path; the others raise on use.
 _ON_PATH = {'VanillaVAE': VanillaVAE, 'BetaVAE': BetaVAE, 'IWAE': IWAE, 'VQVAE': VQVAE, 'Autoencoder': Autoencoder,
-            'InfoVAE': InfoVAE, 'DIPVAE': DIPVAE, 'MIWAE': MIWAE}
+            'InfoVAE': InfoVAE, 'DIPVAE': DIPVAE, 'MIWAE': MIWAE, 'LogCoshVAE': LogCoshVAE}
 _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 'DIPVAE', 'BetaVAE', 'InfoVAE',
                     'WAE_MMD', 'VampVAE', 'GammaVAE', 'MSSIMVAE', 'JointVAE', 'BetaTCVAE', 'FactorVAE',
                     'LogCoshVAE', 'VanillaVAE', 'ConditionalVAE', 'CategoricalVAE', 'Autoencoder']
@@ -1002,8 +1065,8 @@ _REFERENCE_NAMES = ['HVAE', 'LVAE', 'IWAE', 'SWAE', 'MIWAE', 'VQVAE', 'DFCVAE', 
 def _not_on_path(name):
     def ctor(*args, **kwargs):
         raise NotImplementedError(f"{name} is not on the MI355X training path of this build "
-                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE, DIPVAE, MIWAE are; "
-                                  f"DESIGN.md §7)")
+                                  f"(VanillaVAE, BetaVAE, IWAE, VQVAE, Autoencoder, InfoVAE, DIPVAE, MIWAE, LogCoshVAE "
+                                  f"are; DESIGN.md §7)")
     return ctor
 
 
