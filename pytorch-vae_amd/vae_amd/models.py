@@ -40,6 +40,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib as L
+from .closers import LogCoshLoss, ReconLoss
 from .net import StepPlan, VAENet
 
 Tensor = torch.Tensor
@@ -196,58 +197,36 @@ class _HipELBO(torch.autograd.Function):
         return plan.grads.clone(), None, None, None, None, None
 
 
-class _HipReconLoss(torch.autograd.Function):
-    """The Autoencoder's centre-weighted MSE / MS-SSIM on the GPU (vaehip.h vae_recon_loss): forward
-    evaluates the loss and dL/drecons in one call; backward scales that seed by dL/dloss.  `cfg` is a
+class _HipCloser(torch.autograd.Function):
+    """A closing loss (vae_amd/closers.py) on the drop-in's tensors: forward evaluates the loss and
+    dL/drecons in one call; backward scales that seed by dL/dloss."""
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None
+
+
+class _HipReconLoss(_HipCloser):
+    """The Autoencoder's centre-weighted MSE / MS-SSIM on the GPU (vaehip.h vae_recon_loss).  `cfg` is a
     StepPlan recon_loss dict."""
 
     @staticmethod
     def forward(ctx, recons: Tensor, target: Tensor, cfg: dict):
-        n, c, h, w = recons.shape
-        recons, target = recons.detach().float().contiguous(), target.detach().float().contiguous()
-        if cfg["kind"] == "center":
-            mask = cfg["mask"].to(recons.device, torch.float32).contiguous()
-            a = L.recon_loss_args(L.RLOSS_CENTER, n, c, h, w, mask=mask)
-        else:
-            a = L.recon_loss_args(L.RLOSS_MSSIM, n, c, h, w, window=cfg["window"], levels=cfg.get("levels", 5),
-                                  normalize=cfg.get("normalize", True))
-        grad = torch.empty_like(recons)
-        out = torch.zeros(3, dtype=torch.float32, device=recons.device)
-        ws = torch.empty(max(1, L.recon_loss_workspace(a) // 4), dtype=torch.float32, device=recons.device)
-        a.recon, a.target, a.grad, a.out = recons.data_ptr(), target.data_ptr(), grad.data_ptr(), out.data_ptr()
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 4
-        L.call("vae_recon_loss", a, L.stream_ptr())
+        loss, grad = ReconLoss.evaluate(recons, target, cfg)
         ctx.save_for_backward(grad)
-        return out[0].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None
+        return loss
 
 
-class _HipLogCosh(torch.autograd.Function):
+class _HipLogCosh(_HipCloser):
     """LogCoshVAE's reconstruction term (1/alpha) mean log cosh(alpha (recons - input)) on the GPU
-    (vaehip.h vae_logcosh_loss, called without mulv): forward evaluates the term and dL/drecons =
-    tanh(alpha t) / N in one call; backward scales that seed by dL/dloss."""
+    (vaehip.h vae_logcosh_loss, called without mulv); dL/drecons = tanh(alpha t) / N."""
 
     @staticmethod
     def forward(ctx, recons: Tensor, target: Tensor, alpha: float):
-        recons, target = recons.detach().float().contiguous(), target.detach().float().contiguous()
-        a = L.logcosh_args(recons.shape[0], recons[0].numel(), alpha)
-        grad = torch.empty_like(recons)
-        out = torch.zeros(4, dtype=torch.float32, device=recons.device)
-        ws = torch.empty(max(1, L.logcosh_workspace(a) // 8), dtype=torch.float64, device=recons.device)
-        a.recon, a.target, a.grad, a.out = recons.data_ptr(), target.data_ptr(), grad.data_ptr(), out.data_ptr()
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
-        L.call("vae_logcosh_loss", a, L.stream_ptr())
+        loss, grad = LogCoshLoss.evaluate(recons, target, alpha)
         ctx.save_for_backward(grad)
-        return out[1].clone()
-
-    @staticmethod
-    def backward(ctx, g):
-        (grad,) = ctx.saved_tensors
-        return grad * g, None, None
+        return loss
 
 
 class _HipVAE(BaseVAE):
@@ -651,7 +630,7 @@ class LogCoshVAE(_HipVAE):
         """logcosh_vae.py:125-155."""
         recons, input, mu, log_var = args[0], args[1], args[2], args[3]
         kld_weight = kwargs['M_N']
-        if recons.is_cuda and recons.dim() == 4 and recons.shape == input.shape and float(self.alpha) > 0.0:
+        if LogCoshLoss.takes(self.alpha, recons, input):
             recons_loss = _HipLogCosh.apply(recons, input, float(self.alpha))   # vae_logcosh_loss (forward + seed)
         else:
             recons_loss = self.logcosh(recons - input, self.alpha).mean()
@@ -914,15 +893,8 @@ class Autoencoder(_HipVAE):
         g = self._gpu_loss(args, kld_weight=0.0) if self.center_focus_sigma is None and self.mssim is None else None
         if g is not None:
             return {**g, 'KLD': zero, 'feature_loss': zero}
-        cfg = (self._recon_loss_cfg(recons.device) if recons.is_cuda and recons.dim() == 4
-               and recons.shape[2] * recons.shape[3] <= 4096 and recons.shape[2:] == input.shape[2:] else None)
-        if cfg is not None and cfg["kind"] == "mssim":
-            # the kernel's pyramid halves exactly (vaehip.h vae_recon_loss); other plane sizes (the
-            # reference's avg_pool2d floors them, mssim_vae.py) take the torch MS-SSIM below
-            step = 1 << (cfg.get("levels", 5) - 1)
-            if recons.shape[2] % step or recons.shape[3] % step:
-                cfg = None
-        if cfg is not None and (cfg["kind"] != "center" or tuple(cfg["mask"].shape) == tuple(recons.shape[2:])):
+        cfg = self._recon_loss_cfg(recons.device) if ReconLoss.takes_planes(recons, input) else None
+        if ReconLoss.takes(cfg, recons, input):       # (the calls the kernel does not take: torch, below)
             recons_loss = _HipReconLoss.apply(recons, input, cfg)  # vae_recon_loss (HIP forward + seed)
         elif self.center_focus_sigma is not None:
             if self.center_weight_mask is None:

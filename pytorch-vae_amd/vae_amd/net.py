@@ -24,6 +24,7 @@ from . import _lib as L
 from .calls import BATCH_FN, batch_filter_calls, call_one, run_calls, size_workspaces, structs  # noqa: F401
 from .layout import reference_key_order, vanilla_layout
 from .plan import NetBase, PlanBase, ZeroRegion, _pad4, make_swaps                              # noqa: F401
+from .closers import CLOSERS, ReconLoss
 from .terms import MMD_KINDS, TERMS
 
 SLOPE = 0.01         # nn.LeakyReLU default
@@ -84,6 +85,8 @@ class StepPlan(PlanBase):
     InfoVAE's) and beta; vae_logcosh_loss closes its forward in place of the ELBO and seeds the backward
     with dL/drecon (grad_recon) and the KL coefficient beta*kld_weight/B (kl_coef).
     Such a batch-coupled latent term is `self.term` (terms.py) of a training plan, None otherwise.
+    A loss that closes the forward in place of the ELBO — recon_loss=, or a loss in CLOSERS — is
+    `self.closer` (closers.py) of a fused training plan, None otherwise.
     grads land in `self.grads` (same layout as net.params); `zero` (grads, BN sums, SSE,
     d[mu|logvar]) is cleared by `vae_step_begin` at the start of every step."""
 
@@ -102,12 +105,8 @@ class StepPlan(PlanBase):
         # batch_wgrads = False keep the generic per-op calls in place of the dedicated bottleneck
         # kernels, the 64/128-channel head kernels, the 8-channel padded RGB ends, materialised
         # BatchNorm operands for layers >= mat_min_flops, and the batched weight gradients.
-        if loss == "logcosh":
-            # (alpha's default is InfoVAE's: the log-cosh plan has to be given its own)
-            if recon_loss is not None or samples != 1:
-                raise ValueError("StepPlan(loss='logcosh') takes one sample and no recon_loss")
-            if not 0.0 < float(alpha) < float("inf"):
-                raise ValueError(f"StepPlan(loss='logcosh') needs a finite alpha > 0, got {alpha}")
+        if loss in CLOSERS:
+            CLOSERS[loss].check(alpha=alpha, samples=samples, recon_loss=recon_loss)
         super().__init__(net)
         self.materialise, self.mat_min_flops = bool(materialise), float(mat_min_flops)
         self.batch_wgrads_on = bool(batch_wgrads)
@@ -115,19 +114,13 @@ class StepPlan(PlanBase):
         # vae_conv_args.deterministic), so two runs of the same step give bit-identical gradients;
         # the default for fp32 (parity) plans, unsupported by the bf16 kernels.
         self.deterministic = (net.dtype == torch.float32) if deterministic is None else bool(deterministic)
-        # recon_loss (the Autoencoder's other reconstruction losses, vaehip.h vae_recon_loss):
-        # {"kind": "center", "mask": [H][W] device tensor} or {"kind": "mssim", "window": 1-D window}.
-        # The loss runs inside the step in place of the ELBO and seeds the backward with its
-        # dL/drecon (grad_recon), as the drop-in path does with autograd's.
-        self.recon_loss = recon_loss if training else None
-        # logcosh: the log-cosh reconstruction term and the KL on vae_logcosh_loss (fused training
-        # plans; the drop-in's loss is the caller's, an eval plan has no loss call)
-        self._logcosh_plan = loss == "logcosh"
-        self.logcosh = (dict(alpha=float(alpha), beta=float(beta)) if loss == "logcosh" and training and fused_loss
-                        else None)
-        # own_seed: the loss call closing the forward writes dL/drecon itself (no ELBO kernel)
-        self.own_seed = self.recon_loss is not None or self.logcosh is not None
-        self.seed_recon = (not fused_loss) or self.own_seed
+        # closing: the class of the loss that closes the forward in place of the ELBO and seeds the
+        # backward with its dL/drecon (grad_recon), as the drop-in path does with autograd's —
+        # recon_loss= (the Autoencoder's other reconstruction losses: {"kind": "center", "mask": [H][W]
+        # tensor} or {"kind": "mssim", "window": 1-D window}) or a loss in CLOSERS.  Fused training plans
+        # only: the drop-in's loss is the caller's, an eval plan has no loss call.
+        closing = (ReconLoss if recon_loss is not None else CLOSERS.get(loss)) if training and fused_loss else None
+        self.seed_recon = (not fused_loss) or closing is not None
         self.B = batch
         # training=False: eval-mode BatchNorm (running statistics, nothing updated; the
         # reference's validation_step / sample / generate under model.eval()) — forward only
@@ -155,7 +148,7 @@ class StepPlan(PlanBase):
             if not 1 <= batch <= 1024:
                 raise ValueError(f"StepPlan(loss='miwae') takes 1..1024 images a batch (vae_elbo_fwd), got {batch}")
         self.S = samples if loss == "iwae" else (self.M * int(samples) if loss == "miwae" else 1)
-        self.loss_kind = self.LOSS_KINDS[loss]
+        self.loss, self.loss_kind = loss, self.LOSS_KINDS[loss]
         self.kld_weight, self.beta, self.gamma = kld_weight, beta, gamma
         if kernel_type not in MMD_KINDS:
             raise ValueError('Undefined kernel type.')                   # info_vae.py:173
@@ -270,6 +263,9 @@ class StepPlan(PlanBase):
         if loss in TERMS and training:
             self.term = TERMS[loss](self, alpha=alpha, reg_weight=reg_weight, kernel_type=kernel_type,
                                     latent_var=latent_var, lambda_diag=lambda_diag, lambda_offdiag=lambda_offdiag)
+        self.closer = None
+        if closing is not None:
+            self.closer = closing.for_plan(self, recon_loss=recon_loss, alpha=alpha, beta=beta)
         self._build()
         if fuse_bn and training:
             # each BatchNorm finalisation carried by the call that produces its statistics
@@ -611,17 +607,15 @@ class StepPlan(PlanBase):
         # extra workgroup of its filter-partial reduction, the seed coefficient a constant) instead
         # of a vae_elbo_fwd launch between the forward and the backward — the bf16 head kernels,
         # the vanilla / BetaVAE-H losses (their seeds do not depend on the batch), one sample
-        self.elbo_in_head = (self.fused_loss and self.training and not self.own_seed and not self.wide_head
+        self.elbo_in_head = (self.fused_loss and self.training and self.closer is None and not self.wide_head
                              and self.S == 1 and T == L.BF16 and B <= 1024
                              and self.loss_kind in (L.LOSS_VANILLA, L.LOSS_BETA_H))
         # (with elbo_in_head, out / per_img / head_coef / kl_coef are written by the backward: they
         # are this step's only after backward() — loss_dict() raises in between)
-        if self.recon_loss is not None:
-            self._add_recon_loss(F)
-        elif self.logcosh is not None:
-            self._add_logcosh_loss(F)
-        elif self.fused_loss and not self.elbo_in_head and not self._logcosh_plan:
-            # (an eval log-cosh plan has no loss call: its loss is the caller's, never the ELBO's)
+        if self.closer is not None:
+            self.closer.join(self, F)
+        elif self.fused_loss and not self.elbo_in_head and self.loss not in CLOSERS:
+            # (an eval plan of a loss in CLOSERS has no loss call: its loss is the caller's, never the ELBO's)
             self._add(F, "vae_elbo_fwd", e)
 
     def _bwd_head(self, Bw):
@@ -742,40 +736,6 @@ class StepPlan(PlanBase):
                 self.bwd_sums(a, enc_pre[i - 1])
                 self._add(Bw, "vae_conv2d_bwd_data", a)
 
-    def _add_recon_loss(self, F):
-        """The recon_loss call closing the forward (vae_recon_loss): loss terms into `out`, per-image
-        MSE from the head's SSE, and dL/drecon into grad_recon for the backward."""
-        img, BS = self.net.img_size, self.B * self.S
-        cfg = self.recon_loss
-        if cfg["kind"] == "center":
-            self._rl_mask = cfg["mask"].to(self.net.device, torch.float32).contiguous().view(img, img)
-            a = L.recon_loss_args(L.RLOSS_CENTER, BS, 3, img, img, mask=self._rl_mask)
-        elif cfg["kind"] == "mssim":
-            a = L.recon_loss_args(L.RLOSS_MSSIM, BS, 3, img, img, window=cfg["window"],
-                                  levels=cfg.get("levels", 5), normalize=cfg.get("normalize", True))
-        else:
-            raise ValueError(f"recon_loss kind {cfg['kind']!r}")
-        a.recon, a.target, a.grad, a.out = (self.recon.data_ptr(), self.x.data_ptr(), self.grad_recon.data_ptr(),
-                                            self.out.data_ptr())
-        a.sse, a.per_img = self.sse.data_ptr(), self.per_img.data_ptr()
-        self._rl_ws = torch.zeros(max(1, L.recon_loss_workspace(a) // 4), dtype=torch.float32, device=self.net.device)
-        a.workspace, a.workspace_bytes = self._rl_ws.data_ptr(), self._rl_ws.numel() * 4
-        self._add(F, "vae_recon_loss", a)
-
-    def _add_logcosh_loss(self, F):
-        """The vae_logcosh_loss call closing the forward: loss terms into `out`, per-image MSE from the
-        head's SSE, dL/drecon into grad_recon and the KL coefficient beta*kld_weight/B into kl_coef."""
-        img, B = self.net.img_size, self.B
-        a = L.logcosh_args(B, 3 * img * img, self.logcosh["alpha"], latent=self.net.latent_dim,
-                           kl_weight=self.logcosh["beta"] * self.kld_weight)
-        a.recon, a.target, a.grad, a.out = (self.recon.data_ptr(), self.x.data_ptr(), self.grad_recon.data_ptr(),
-                                            self.out.data_ptr())
-        a.mulv, a.kl_coef = self.mulv.data_ptr(), self.kl_coef.data_ptr()
-        a.sse, a.per_img = self.sse.data_ptr(), self.per_img.data_ptr()
-        self._lc_ws = torch.zeros(max(1, L.logcosh_workspace(a) // 8), dtype=torch.float64, device=self.net.device)
-        a.workspace, a.workspace_bytes = self._lc_ws.data_ptr(), self._lc_ws.numel() * 8
-        self._add(F, "vae_logcosh_loss", a)
-
     def _wide_head_fwd(self, F):
         """Head of a final layer wider than 32 channels: Conv2d(C -> 3 padded to 8, k3 s1 p1) on the
         conv-GEMM path with BatchNorm+LeakyReLU applied to its input on load, then vae_recon_fwd:
@@ -789,7 +749,7 @@ class StepPlan(PlanBase):
         self._add(F, "vae_conv2d_fwd", a)
         rc = L.ReconArgs(dtype=T, n=BS, h=img, w=img, c=3, ld=8)
         rc.y, rc.target, rc.recon, rc.sse = self.y8.data_ptr(), self.x.data_ptr(), self.recon.data_ptr(), self.sse.data_ptr()
-        if self.fused_loss and self.training and not self.own_seed:
+        if self.fused_loss and self.training and self.closer is None:
             # (DIP-VAE's reconstruction term is the sum, dip_vae.py:141: no 1/(B*3*H*W))
             rc.dy = self.g8.data_ptr()
             recon_sum = self.term is not None and self.term.recon_sum
@@ -881,9 +841,9 @@ class StepPlan(PlanBase):
     # dL/drecon and dL/d[mu|log_var].
     LOSS_KINDS = {"vanilla": L.LOSS_VANILLA, "betaH": L.LOSS_BETA_H, "betaB": L.LOSS_BETA_B,
                   "iwae": L.LOSS_IWAE, "info": L.LOSS_INFO, "dip": L.LOSS_DIP, "miwae": L.LOSS_MIWAE,
-                  # (LogCoshVAE has no vae_loss_kind: its loss is vae_logcosh_loss; the drop-in plan and the
-                  # eval plan are the vanilla ones)
-                  "logcosh": L.LOSS_VANILLA}
+                  # (a loss in CLOSERS has no vae_loss_kind: its drop-in plan and its eval plan are the
+                  # vanilla ones)
+                  **{name: L.LOSS_VANILLA for name in CLOSERS}}
 
     def run_elbo(self, stream, loss: str, kld_weight: float, beta: float = 4.0, gamma: float = 1000.0,
                  max_capacity: float = 25.0, capacity_max_iter: float = 1e5, num_iter: Optional[int] = None,
@@ -893,9 +853,9 @@ class StepPlan(PlanBase):
         as the reference reports it, raw KLD]; per_img; head_coef / kl_coef = dloss/dsse_i and the
         per-row KL gradient coefficient (the backward seeds).  The loss arguments are spelled as the
         constructor's; c_max / c_stop_iter are the older names of max_capacity / capacity_max_iter."""
-        if loss == "logcosh":
-            raise ValueError("run_elbo('logcosh'): LogCoshVAE's loss runs on vae_logcosh_loss "
-                             "(StepPlan(loss='logcosh'), models.LogCoshVAE.loss_function), not on the ELBO kernel")
+        if loss in CLOSERS:
+            raise ValueError(f"run_elbo({loss!r}): this loss runs on {CLOSERS[loss].fn} (StepPlan(loss={loss!r}), "
+                             f"the model's loss_function), not on the ELBO kernel")
         e = self.elbo_args
         e.kind = self.LOSS_KINDS[loss]
         if e.kind == L.LOSS_MIWAE:

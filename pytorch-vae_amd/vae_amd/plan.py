@@ -136,6 +136,7 @@ class PlanBase:
     side_all = True         # every SIDE_FNS call runs there (False: only the batches marked .side)
     wg_overlap = False      # the decoder's weight gradients as a side-stream batch (StepPlan)
     elbo_in_head = False    # the loss is evaluated by the head backward, not by the forward
+    closer = None           # the loss that closes the forward in place of the ELBO (closers.py)
     term = None             # the loss's batch-coupled latent term (terms.py); answers the next two
     prior = None            # InfoVAE's prior sample (an input of the step)
     extra_term = None       # (name, one-element tensor): a fourth loss-dict entry (MMD, DIP_Loss)

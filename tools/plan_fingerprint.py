@@ -32,6 +32,8 @@ import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 AE_BIG = [128, 256, 512, 1024, 2048]
+WIDE = [64, 64, 128, 256, 512]          # with head_kernels=False: the head on the conv-GEMM route
+CENTER = {"kind": "center", "mask": torch.ones(64, 64)}
 # name -> (net kind, net arguments, batch, plan arguments); bf16 unless "fp32" is in the name
 CONFIGS = {
     "vanilla_b64": ("vae", {}, 64, {}),
@@ -41,7 +43,7 @@ CONFIGS = {
     "ae_big_b8": ("vae", dict(hidden_dims=AE_BIG), 8, dict(kld_weight=0.0)),
     "per_op_b16": ("vae", {}, 16, dict(latent_kernels=False, pad_rgb=False)),
     "unbatched_b16": ("vae", {}, 16, dict(batch_wgrads=False)),
-    "gemm_head_b4": ("vae", dict(hidden_dims=[64, 64, 128, 256, 512]), 4, dict(head_kernels=False)),
+    "gemm_head_b4": ("vae", dict(hidden_dims=WIDE), 4, dict(head_kernels=False)),
     "fuse_bn_b4": ("vae", {}, 4, dict(fuse_bn=True, bn_in_consumer=False)),
     "dropin_train_b4": ("vae", {}, 4, dict(fused_loss=False)),
     "dropin_eval_b4": ("vae", {}, 4, dict(fused_loss=False, training=False)),
@@ -57,7 +59,18 @@ CONFIGS = {
     "miwae_dropin_b2": ("vae", {}, 2, dict(loss="miwae", fused_loss=False, samples=2, estimates=2)),
     "info_per_op_b16": ("vae", {}, 16, dict(loss="info", latent_kernels=False)),
     "dip_fp32_b4": ("vae", {}, 4, dict(loss="dip")),
-    "center_b4": ("vae", {}, 4, dict(recon_loss={"kind": "center", "mask": torch.ones(64, 64)}, kld_weight=0.0)),
+    "center_b4": ("vae", {}, 4, dict(recon_loss=CENTER, kld_weight=0.0)),
+    # the losses that close the forward themselves (vae_amd/closers.py), with their drop-in and eval
+    # plans, which have no loss call, and the wide head under a closer
+    "logcosh_b16": ("vae", {}, 16, dict(loss="logcosh", alpha=10.0, beta=2.0, kld_weight=2.5e-4)),
+    "logcosh_per_op_b4": ("vae", {}, 4, dict(loss="logcosh", alpha=10.0, latent_kernels=False, pad_rgb=False)),
+    "logcosh_fp32_b4": ("vae", {}, 4, dict(loss="logcosh", alpha=10.0)),
+    "logcosh_dropin_b4": ("vae", {}, 4, dict(loss="logcosh", alpha=10.0, fused_loss=False)),
+    "logcosh_eval_b4": ("vae", {}, 4, dict(loss="logcosh", alpha=10.0, training=False)),
+    "logcosh_wide_b4": ("vae", dict(hidden_dims=WIDE), 4, dict(loss="logcosh", alpha=10.0, head_kernels=False)),
+    "mssim_b4": ("vae", {}, 4, dict(recon_loss={"kind": "mssim", "window": [1 / 11] * 11}, kld_weight=0.0)),
+    "center_wide_b4": ("vae", dict(hidden_dims=WIDE), 4, dict(recon_loss=CENTER, kld_weight=0.0, head_kernels=False)),
+    "center_eval_b4": ("vae", {}, 4, dict(recon_loss=CENTER, kld_weight=0.0, training=False, fused_loss=False)),
 }
 
 
